@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- whole-job throughput of the MI355X-native --indep-pairwise hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: it sets the workload up, runs W warm-up steps, times K steps, writes the last timed step's
+prune set to DIR with --dump-outputs, and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+workload's `config`, and `roofline` / `stage_ms` from the timed steps' own counters).  Everything else below -- the legs, the CPU baseline
+and end-to-end runs of both binaries, the in-run PMC passes and ceiling microbenchmarks, the bits check, power / clock sampling and the
+N-rank self-check -- runs only with --full.
 
 ONE workload family at every N (synthetic; one genome of 22 autosomes with variant counts proportional to GRCh38 lengths, uniform
 spacing, chromosomes = subcontigs LPT-sharded over the ranks exactly as `ldp_set_shard` does it):
@@ -815,6 +821,22 @@ def flatten_summary(out):
         r["e2e_plink2_hip_gpus_identical_to_one_gpu"] = n.get("identical_to_one_gpu")
 
 
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, removed):
+    """--dump-outputs: the last timed step's result as a caller of the path receives it, the prune set over the whole genome, one float32
+    per variant (1 = removed) in DIR/prune_removed.npy.  Where that would exceed DUMP_CAP_BYTES, a fixed sample of the variants (seeded
+    by SEED) is written instead, their indices beside it in DIR/prune_removed_index.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    mask = np.asarray(removed, dtype=bool)
+    if mask.size * 4 > DUMP_CAP_BYTES:
+        idx = np.sort(np.random.default_rng(SEED).choice(mask.size, size=DUMP_CAP_BYTES // 12, replace=False))
+        np.save(os.path.join(directory, "prune_removed_index.npy"), idx.astype(np.float64))
+        mask = mask[idx]
+    np.save(os.path.join(directory, "prune_removed.npy"), mask.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -841,6 +863,9 @@ def main():
     ap.add_argument("--tile", type=int, default=65536, help="side of the config4_tiles leg's cross-chromosome tile set")
     ap.add_argument("--only-config4", action="store_true", help="run the config4_tiles leg alone and print it as the line (the PMC profile of that shape: tools/profile.sh)")
     ap.add_argument("--option", action="append", default=[], help="name=value: a per-engine kernel switch (ldp_debug_set_option) for the main workload, for experiments")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: legs, CPU baseline, end-to-end runs, PMC passes, ceilings, "
+                                                        "bits check, power / clock sampling, N-rank self-check (the --no-* switches above act within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     import torch
@@ -943,7 +968,7 @@ def main():
     # (config5: runs of 400 consecutive multiallelic variants, one ldp_load_pgen_records call each -- a loader hands over records in batches --, 2 % of the rank's share)
     main_multi = (max(1, int(round(multi_frac * (per_gpu_variants or cfg["variants"] // world) / 400.0))), 400) if multi_frac > 0 else None
     wl = Workload(pkg, torch, cfg, args.missing_rate, rank, world, local_rank, main_options, main_multi)
-    smi = support.SmiSampler() if rank == 0 else None
+    smi = support.SmiSampler() if (rank == 0 and args.full) else None
 
     def open_window():
         if smi:
@@ -954,6 +979,8 @@ def main():
         smi.stop()
     ctr = ks[-1]
     removed = distmod.bitmap_to_mask(removed.cpu().numpy() if use_dist else removed, cfg["variants"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, removed)
     per_rank_pairs = [ctr["candidate_pairs"]]
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_device)
@@ -967,7 +994,7 @@ def main():
     # ---- self-check of an N-rank run (every rank takes part; rank 0 reports): the world really has N ranks, every rank sits on a
     # device of its own, and the collective backend saw every rank
     selfcheck = None
-    if use_dist:
+    if use_dist and args.full:
         props = torch.cuda.get_device_properties(local_rank)
         ident = "%s/%s" % (getattr(props, "uuid", None) or getattr(props, "pci_bus_id", local_rank), getattr(props, "pci_device_id", ""))
         ids = [None] * world
@@ -1018,7 +1045,7 @@ def main():
             "stage_ms": stage_ms(cmean, wl.image_bytes),
             "power_and_clock": smi.summary("main") if smi else None,
         }
-        if world == 1 and not args.no_legs:   # (profiling runs -- tools/profile.sh, the in-run PMC passes -- carry the timed step's kernels only)
+        if world == 1 and args.full and not args.no_legs:   # (profiling runs -- tools/profile.sh, the in-run PMC passes -- carry the timed step's kernels only)
             try:
                 out["headline_bits_check"] = headline_bits_check(pkg, torch, wl, removed)
             except Exception as ex:  # pragma: no cover
@@ -1026,7 +1053,7 @@ def main():
         if selfcheck is not None:
             out["multi_rank_selfcheck"] = selfcheck
     subset = None
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         subset = (wl.founder_ct, wl.window_bp, cfg["r2"], wl.chr_idx, wl.bps, wl.m_total)
     wl.close()
     if subset is not None:
@@ -1052,7 +1079,7 @@ def main():
                 "what": "chr20-22 of the genome run alone through ONE engine on rank 0 against the stitched bitmap of the %d ranks" % world}
         except Exception as ex:  # pragma: no cover
             out["multi_rank_selfcheck"]["three_chromosome_subset"] = {"error": str(ex)[:300]}
-    if rank == 0 and world == 1 and not (args.no_pmc or args.no_legs or args.no_cpu_baseline):
+    if rank == 0 and world == 1 and args.full and not (args.no_pmc or args.no_legs or args.no_cpu_baseline):
         # roofline.traffic of the headline workload, measured here and now (the device is free: the share has just been released)
         wargs = ["--workload", name] + (["--strong"] if strong else [])
         for flag, v in (("--samples", args.samples), ("--variants", args.variants), ("--window-kb", args.window_kb), ("--r2", args.r2), ("--spacing", args.spacing)):
@@ -1079,7 +1106,7 @@ def main():
         # the metric's wall-clock leg: materialise the chr22-sized fileset and let the reference run (twice: fixed-width file, variable-width file) beside
         # whatever this script does next.  Called AFTER the legs whose numbers are walls per step: two reference processes and a 256-thread --make-pgen
         # on the host stretched those walls by 10-70 % when they ran beside them (profiles/r06_experiments.md); kernel times never moved.
-        if e2e_box[0] is not None or not (rank == 0 and world == 1 and (not args.no_cpu_baseline) and (not args.no_e2e) and (not args.no_cli_compare) and cfg["samples"] > 100000):
+        if e2e_box[0] is not None or not (rank == 0 and world == 1 and args.full and (not args.no_cpu_baseline) and (not args.no_e2e) and (not args.no_cli_compare) and cfg["samples"] > 100000):
             return
         try:
             e2e_box[0] = support.E2EChr22(pkg, torch, cfg, args.e2e_variants or int(round(CONFIGS[name]["variants"] * CHR22_FRACTION)), SEED, genome_layout)
@@ -1088,7 +1115,7 @@ def main():
             e2e_box[0] = None
             out["e2e_error"] = str(ex)[:300]
 
-    if rank == 0 and world == 1 and not args.no_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_legs:
         legs = {}
         half = max(2, min(args.steps, 10) // 2)
 
@@ -1198,7 +1225,7 @@ def main():
     start_e2e()   # (no legs in this run: start it here)
     e2e = e2e_box[0]
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             m = args.cpu_sample_variants or (440000 if cfg["samples"] <= 100000 else 11000)  # ~2-20 s of reference time either way
             cb = cpu_baseline(pkg, torch, cfg["samples"], m, cfg["spacing"], cfg["window_kb"], cfg["r2"], args.missing_rate, cli_compare=not args.no_cli_compare)
             if e2e is not None:
@@ -1229,8 +1256,8 @@ def main():
             out["cpu_baseline"] = cb
         else:
             out["cpu_baseline"] = {"value": None, "unit": "variant-pairs/s", "cores": 0, "kind": "reference",
-                                   "sample": "measured at N=1 only", **host_description()}
-        if world > 1 and (not args.no_e2e) and cfg["samples"] > 100000:
+                                   "sample": "measured at N=1 only" if args.full else "measured with --full only", **host_description()}
+        if world > 1 and args.full and (not args.no_e2e) and cfg["samples"] > 100000:
             # the wall-clock half of the metric at N GPUs: `plink2-hip --gpus N` (one feeding thread per engine, each next to its device, the shards' rows
             # crossing N PCIe links at once) end to end on the chr22-sized fileset, and `--gpus 1` on the same files beside it.  The other ranks wait at the
             # final barrier with their shares still resident (a chr22-sized shard is 22 GB / N per device).

@@ -65,3 +65,21 @@ def test_bench_support_is_importable_without_a_gpu():
     import bench_support as support
     assert support.REF_BIN.endswith("oracle/_ref/plink2") and support.CLI_BIN.endswith("plink-ng_amd/bin/plink2-hip")
     assert support._PHASES.search("[timing] setup+parse 0.081 s | genotype load (file -> HBM bit-planes) 0.516 s | run 0.064 s (pair kernel 41.6 ms, replay 0.6 ms; 272029960 candidate pairs) | x")
+
+
+def test_dump_outputs_writes_the_prune_set_and_a_fixed_sample_above_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    removed = np.random.default_rng(3).random(1000) < 0.3
+    bench.dump_outputs(str(tmp_path / "a"), removed)
+    got = np.load(str(tmp_path / "a" / "prune_removed.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, removed.astype(np.float32))
+    assert not (tmp_path / "a" / "prune_removed_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 1200)   # (4 bytes per variant would be 4,000: a sample of 100 variants, 12 bytes each)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), removed)
+    idx = np.load(str(tmp_path / "b" / "prune_removed_index.npy"))
+    sample = np.load(str(tmp_path / "b" / "prune_removed.npy"))
+    assert idx.dtype == np.float64 and len(idx) == 100 and sample.nbytes + idx.nbytes <= 1200
+    assert np.array_equal(sample, removed[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(str(tmp_path / "c" / "prune_removed_index.npy")))   # the same sample every run

@@ -94,7 +94,7 @@ def test_bench_n_ranks_on_one_device(gpu_pkg, tmp_path, world):
     prune set has as many variants as the single-rank run over the same total workload (strong scaling: the same genome)."""
     env = dict(os.environ, LDP_BENCH_ALIAS_DEVICES="1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    common = ["--steps", "2", "--warmup", "1", "--workload", "config2", "--variants", "90000", "--samples", "20000", "--strong", "--no-cpu-baseline", "--no-legs"]
+    common = ["--steps", "2", "--warmup", "1", "--workload", "config2", "--variants", "90000", "--samples", "20000", "--strong", "--no-cpu-baseline", "--no-legs", "--full"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29590 + world),
            os.path.join(REPO, "bench.py"), "--gpus", str(world)] + common
     cp = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -122,7 +122,7 @@ def test_bench_n_ranks_time_plink2_hip_end_to_end(gpu_pkg):
     env = dict(os.environ, LDP_BENCH_ALIAS_DEVICES="1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     args = ["--steps", "1", "--warmup", "1", "--workload", "config2", "--variants", "40000", "--samples", "100032", "--strong", "--no-cpu-baseline", "--no-legs",
-            "--e2e-variants", "3000"]
+            "--e2e-variants", "3000", "--full"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", "29617",
            os.path.join(REPO, "bench.py"), "--gpus", str(world)] + args
     cp = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -154,3 +154,26 @@ def test_bench_share_that_does_not_fit_hbm(gpu_pkg):
     j2 = json.loads([ln for ln in cp2.stdout.splitlines() if ln.startswith("{")][-1])
     assert j2["config"]["resident"] is True and j2["config"]["candidate_pairs_total"] == j["config"]["candidate_pairs_total"]
     assert j2["data"] == "synthetic" and j2["scaling"] == "weak"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_prune_set(gpu_pkg, tmp_path):
+    """A plain bench.py run times the step count it is given and reports the headline only (no legs, reference runs, bits check, power
+    sampling or self-check: those are --full's); with --dump-outputs it writes the last timed step's prune set, the same from two runs of
+    the same arguments."""
+    args = ["--steps", "3", "--warmup", "1", "--workload", "config2", "--variants", "60000", "--samples", "20000"]
+    masks = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        cp = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args + ["--dump-outputs", str(d)], cwd=REPO,
+                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert cp.returncode == 0, cp.stderr[-2000:]
+        j = json.loads([ln for ln in cp.stdout.splitlines() if ln.startswith("{")][-1])
+        assert all(key in j for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert not any(key in j for key in ("legs", "headline_bits_check", "multi_rank_selfcheck", "e2e_n_gpus"))
+        assert j["power_and_clock"] is None and j["cpu_baseline"]["value"] is None
+        mask = np.load(str(d / "prune_removed.npy"))
+        assert mask.dtype == np.float32 and mask.shape == (60000,) and int(mask.sum()) == j["config"]["variants_removed"] > 0
+        masks.append(mask)
+    assert np.array_equal(masks[0], masks[1])

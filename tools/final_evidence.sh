@@ -15,7 +15,7 @@ mkdir -p $O
 (LDP_PROF_ARGS="--only-config4" timeout 600 bash tools/profile.sh r05_c4) > $O/prof_c4.log 2>&1
 cd $GRAFT_REPO_ROOT
 for d in gpurun_out/profiles_r05 gpurun_out/profiles_r05_config2 gpurun_out/profiles_r05_c3shape gpurun_out/profiles_r05_c5shape gpurun_out/profiles_r05_miss01 gpurun_out/profiles_r05_miss001 gpurun_out/profiles_r05_c4; do cp $d/* profiles/ 2>/dev/null; done
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err ) 2> $O/bench_n1.time
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err ) 2> $O/bench_n1.time
 (timeout 1200 python -m pytest tests -m gpu -x -q 2>&1 | grep -vE "NCCL|RCCL|rccl" | tail -6) > $O/gpu_suite.txt
 timeout 400 python tests/cli_e2e.py > $O/cli_e2e.txt 2>&1
 timeout 300 python tests/cli_e2e.py --pgen > $O/cli_e2e_pgen.txt 2>&1

@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 df -h /dev/shm /tmp > $O/space.txt 2>&1; nproc >> $O/space.txt; free -g >> $O/space.txt
-( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_full.time
+( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_full.time
 tail -3 $O/bench_full.time; tail -c 600 $O/bench_full.err
 python - <<PY
 import json

@@ -6,7 +6,7 @@ O=$R/gpurun_out/r05c
 mkdir -p $O
 cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_full.time
+( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_full.time
 tail -3 $O/bench_full.time; tail -c 400 $O/bench_full.err
 python - <<PY
 import json

@@ -17,8 +17,8 @@ mkdir -p $O
 (LDP_PROF_ARGS="--only-config4" timeout 600 bash tools/profile.sh r06_c4) > $O/prof_c4.log 2>&1
 cd $GRAFT_REPO_ROOT
 for d in gpurun_out/profiles_r06 gpurun_out/profiles_r06_config2 gpurun_out/profiles_r06_c3shape gpurun_out/profiles_r06_c3miss001 gpurun_out/profiles_r06_c3miss01 gpurun_out/profiles_r06_c5shape gpurun_out/profiles_r06_miss01 gpurun_out/profiles_r06_miss001 gpurun_out/profiles_r06_c4; do cp $d/* profiles/ 2>/dev/null; done
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err ) 2> $O/bench_n1.time
-( time timeout 1500 python bench.py --workload config5 --steps 3 --warmup 1 --no-legs --no-e2e > $O/config5_share.json 2> $O/config5_share.err ) 2> $O/config5_share.time
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err ) 2> $O/bench_n1.time
+( time timeout 1500 python bench.py --workload config5 --steps 3 --warmup 1 --no-legs --no-e2e --full > $O/config5_share.json 2> $O/config5_share.err ) 2> $O/config5_share.time
 ( LDP_BENCH_ALT_MINOR=1 timeout 600 python bench.py --steps 5 --warmup 1 --no-legs --no-cpu-baseline --no-pmc > $O/share_alt_minor.json 2> $O/share_alt_minor.err )
 (timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | grep -vE "NCCL|RCCL|rccl" | tail -6) > $O/gpu_suite.txt
 timeout 400 python tests/cli_e2e.py > $O/cli_e2e.txt 2>&1
