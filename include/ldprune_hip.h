@@ -246,7 +246,9 @@ int ldp_load_genotypes_fd(ldp_engine* e, uint32_t first_variant, uint32_t n, int
  * major one INVERTED (codes 00 <-> 10 swapped: what GenovecInvertUnsafe does to the reference's rows, pgenlib_misc.cc:1090).  Loading the same
  * mapped rows again without rewriting them is fine (the engine knows which rows it inverted); a producer that wants to REWRITE rows it has
  * already loaded calls ldp_map_rows() on them again first -- the call puts them back into the input's orientation and returns when that is
- * done. */
+ * done.  From then on the engine holds rows that its records (major allele, counts, checkpoint statistics) no longer describe, so a call
+ * on an engine that has loaded rows before marks the mapped rows NOT LOADED: ldp_run() fails with LDP_ERR_STATE ("genotypes missing") until
+ * ldp_load_genotypes() has counted them again, rewritten or not. */
 int ldp_map_rows(ldp_engine* e, uint32_t first_variant, uint32_t n, void** device_rows, uint64_t* stride_bytes);
 /* Variant records of a variable-width .pgen file, decoded ON THE DEVICE from the file's own bytes and loaded: what the reference's
  * reader thread does one variant at a time before LdPrune's pair loop (plink2_ld.cc:1345-1390 PgrGetInv1 ->

@@ -19,6 +19,13 @@ extern "C" {
  * touched: this is how the host logic is tested on a CPU-only machine. */
 int ldp_debug_set_variant_recs(ldp_engine* e, const ldp_variant_rec* recs);
 int ldp_debug_replay_pairs(ldp_engine* e, uint64_t n_true, const uint32_t* first, const uint32_t* second, uint64_t* removed);
+/* The decisions of the last run, one byte (0 / 1) per candidate pair in the order of ldp_run_with_stats()'s `stats` array (ldp_get_band()):
+ * the dense predicate rows every pair kernel sets its bits in, copied back from the device as they stand after ldp_run() or
+ * ldp_run_with_stats() -- the production run's, with early termination, routes and launch groups as they were.  *outside_band (optional)
+ * receives the number of bits set in the rows' first / last words OUTSIDE the band (a kernel that writes there is wrong; they are not
+ * part of `out`).  LDP_ERR_STATE when no run has completed since the last load (the rows are cleared group by group as launches are
+ * queued), LDP_ERR_INVALID when capacity < candidate pairs, LDP_ERR_UNSUPPORTED on a sharded engine.  Reads finished results only. */
+int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t* outside_band);
 /* Kernel-selection switches of ONE engine, for tests and measurements (the defaults are what production runs use).  The shipped
  * library reads NO environment variable (csrc/ldp_env.h): this call is the only way to switch anything, engine by engine; only the
  * measurement build (-DLDP_MEASURE, lib/libldprune_hip_measure.so, tools/) presets them from LDP_* variables.  name:

@@ -101,7 +101,7 @@ CABI_SYMBOLS = [
     "ldp_pgen_variant_is_multiallelic", "ldp_pgen_provisional_ref", "ldp_pgen_open_indexed", "ldp_set_r_signed", "ldp_set_variants_vcor_cm", "ldp_pgen_read_alleles", "ldp_pgen_read_phased", "ldp_pgen_read_alleles_phased", "ldp_subset_samples", "ldp_phased_row_bytes", "ldp_phased_phase_offset",
     "ldp_debug_set_option", "ldp_pgen_debug_force_portable", "ldp_matrix_pipe_max_founders", "ldp_map_rows", "ldp_release_device", "ldp_debug_wide_plan",
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
-    "ldp_use_private_copy_threads",
+    "ldp_use_private_copy_threads", "ldp_debug_get_pred",
 ]
 
 
@@ -217,6 +217,7 @@ def lib():
     L.ldp_pair_stats.argtypes = [vp, ctypes.c_uint32, u32p, u32p, vp]
     L.ldp_debug_set_variant_recs.argtypes = [vp, vp]
     L.ldp_debug_replay_pairs.argtypes = [vp, ctypes.c_uint64, u32p, u32p, u64p]
+    L.ldp_debug_get_pred.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64, u64p]
     L.ldp_map_rows.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp), u64p]
     L.ldp_release_device.argtypes = [vp]
     L.ldp_load_pgen_records.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
@@ -807,6 +808,17 @@ class LdPruneEngine:
         bm = self._removed_buf()
         self._ck(self._L.ldp_run_with_stats(self._h, _ptr(bm, ctypes.c_uint64), stats.ctypes.data_as(ctypes.c_void_p), len(stats)))
         return self._to_bool(bm), stats[:cand]
+
+    def last_pred(self, with_outside=False):
+        """The decisions of the last run()/run_with_stats(), one bool per candidate pair in the order of run_with_stats()'s stats
+        (ldp_debug_get_pred: the device's predicate rows as the production kernels left them).  with_outside: also the number of
+        bits the kernels set outside the band (must be 0)."""
+        _, cand = self.band()
+        out = np.zeros(max(cand, 1), dtype=np.uint8)
+        outside = ctypes.c_uint64()
+        self._ck(self._L.ldp_debug_get_pred(self._h, _ptr(out, ctypes.c_uint8), cand, ctypes.byref(outside)))
+        pred = out[:cand].astype(bool)
+        return (pred, int(outside.value)) if with_outside else pred
 
     def pair_stats(self, first, second):
         first, second = _u32(first), _u32(second)

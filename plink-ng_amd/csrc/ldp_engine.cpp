@@ -176,6 +176,7 @@ void free_device(ldp_engine* e) {
   e->d_row_off = nullptr;
   e->d_pair_off = nullptr;
   e->d_pred = nullptr;
+  e->pred_valid = false;
   e->d_items = nullptr;
   e->d_item_general = nullptr;
   e->d_counters = nullptr;

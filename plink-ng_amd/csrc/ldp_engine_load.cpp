@@ -39,6 +39,7 @@ int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void
     return fail(e, LDP_ERR_INVALID, "stride smaller than a genotype row");
   }
   const double t_entry = now_ms();
+  e->pred_valid = false;
   int rc = ensure_device_plan(e);
   if (rc) {
     return rc;
@@ -769,6 +770,13 @@ int ldp_map_rows(ldp_engine* e, uint32_t first_variant, uint32_t n, void** devic
     // rows an earlier load stored inverted (major-allele-oriented image) go back to the input's orientation before the caller sees or
     // rewrites them; the call returns when that is done (the caller writes from a stream of its own)
     HIP_TRY(e, hipSetDevice(e->device));
+    // ... and their records, maj_freqs and checkpoint slots describe rows that are no longer there: launches of the current load epoch are
+    // superseded and the rows count as not loaded until ldp_load_genotypes() has counted them again (ldp_run() refuses the engine meanwhile)
+    const int erc = begin_load_epoch(e);
+    if (erc) {
+      return erc;
+    }
+    std::fill(e->loaded.begin() + l0, e->loaded.begin() + l0 + n, static_cast<uint8_t>(0));
     const hipError_t urc = ldp::launch_unflip_rows(e->d_codes + static_cast<uint64_t>(l0) * e->code_row_bytes, e->code_row_bytes, e->d_stored_inv + l0, n, e->stream);
     if (urc != hipSuccess) {
       return hipfail(e, urc, "unflip_rows_kernel launch");

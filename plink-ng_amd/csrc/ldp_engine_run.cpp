@@ -421,6 +421,7 @@ int reset_launch_counters(ldp_engine* e) {
 // A new load epoch begins (variants are being loaded again): whatever the pair streams still run belongs to the
 // old data.  Order the main stream behind it, forget the launches and clear the counters.
 int begin_load_epoch(ldp_engine* e) {
+  e->pred_valid = false;
   for (int k = 0; k < kPairStreams; ++k) {
     if (e->pair_tail_set[k]) {
       HIP_TRY(e, hipStreamWaitEvent(e->stream, e->pair_tail[k], 0));
@@ -469,6 +470,7 @@ hipError_t queue_route(ldp_engine* e, size_t slot, hipStream_t stream, int allow
 int launch_group(ldp_engine* e, uint32_t gi) {
   ldp_engine::PairGroup& g = e->groups[gi];
   const int k = static_cast<int>(gi % kPairStreams);
+  e->pred_valid = false;  // (the group's predicate rows are cleared below)
   hipStream_t ps = e->pair_stream[k];
   HIP_TRY(e, hipEventRecord(g.ev_ready, e->stream));
   HIP_TRY(e, hipStreamWaitEvent(ps, g.ev_ready, 0));
@@ -574,6 +576,7 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
   }
   const double t_start = now_ms();
   double tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  e->pred_valid = false;
   int rc = ensure_device_plan(e);
   if (rc) {
     return rc;
@@ -855,6 +858,7 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
   e->ctr.ms_replay = replayed ? replay_busy_ms : (t_end - t_replay);  // (time spent replaying, not waiting for groups)
   e->ctr.ms_run_total = t_end - t_start;
   e->ctr.pair_kernel_launches = launches;
+  e->pred_valid = true;  // every group's rows are complete in d_pred until the next load clears them
   return LDP_OK;
 }
 
@@ -877,6 +881,56 @@ int ldp_run_with_stats(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats
     return fail(e, LDP_ERR_INVALID, "stats is NULL");
   }
   return run_impl(e, removed, stats, stats_capacity);
+}
+
+int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t* outside_band) {
+  if (!e) {
+    return LDP_ERR_INVALID;
+  }
+  if (!e->planned || e->matrix_mode || e->band_r2_mode) {
+    return fail(e, LDP_ERR_STATE, "no prune plan (ldp_set_variants)");
+  }
+  if (e->world > 1) {
+    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_debug_get_pred: sharded engines are not supported");
+  }
+  if (!e->pred_valid || (e->pred_words && !e->d_pred)) {
+    return fail(e, LDP_ERR_STATE, "no run has completed since the last load: the predicate rows are not those of a run");
+  }
+  if ((capacity < e->cand_pairs) || (e->cand_pairs && !out)) {
+    return fail(e, LDP_ERR_INVALID, "buffer smaller than the candidate pair count");
+  }
+  std::vector<uint32_t> pred(std::max<size_t>(e->pred_words, 1), 0);
+  if (e->pred_words) {
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipMemcpy(pred.data(), e->d_pred, e->pred_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  // row j: word w holds first variants 32 * ((lo >> 5) + w) + bit; pairs in the order of ldp_run_with_stats() (pair_off)
+  uint64_t outside = 0;
+  for (uint32_t j = 0; j < e->local_ct; ++j) {
+    const uint32_t lo = e->lo_local[j];
+    const uint32_t* row = pred.data() + e->row_off[j];
+    const uint64_t nw = e->row_off[j + 1] - e->row_off[j];
+    uint8_t* dst = out + e->pair_off[j];
+    for (uint32_t i = lo; i < j; ++i) {
+      dst[i - lo] = static_cast<uint8_t>((row[(i >> 5) - (lo >> 5)] >> (i & 31)) & 1u);
+    }
+    for (uint64_t w = 0; w < nw; ++w) {
+      const uint64_t base = (static_cast<uint64_t>(lo >> 5) + w) << 5;  // first variant of bit 0
+      uint32_t in_band = 0xffffffffu;
+      if (base < lo) {
+        in_band &= 0xffffffffu << (lo - base);
+      }
+      if (base + 32 > j) {
+        in_band &= (j > base) ? ((j - base >= 32) ? 0xffffffffu : ((1u << (j - base)) - 1u)) : 0u;
+      }
+      outside += static_cast<uint64_t>(__builtin_popcount(row[w] & ~in_band));
+    }
+  }
+  if (outside_band) {
+    *outside_band = outside;
+  }
+  return LDP_OK;
 }
 
 int ldp_pair_stats(ldp_engine* e, uint32_t n_pairs, const uint32_t* first, const uint32_t* second, ldp_pair_stats_t* out) {

@@ -2,8 +2,10 @@
 """Randomised differential test on the GPU box: the HIP path (early termination on, through the C ABI) against the
 CPU oracle over random shapes -- sample counts around the 512-sample chunk boundaries, count/kb windows with steps,
 both scan orders, thresholds from 0.02 to 0.95, missing rates from 0 to 20 %, LD blocks, monomorphic and all-missing
-rows, several chromosomes.  Prints the first mismatching case (seed) and exits non-zero.
-    python tests/fuzz_parity.py [--cases 150] [--seed 1]"""
+rows, several chromosomes.  Compared per case: the prune set with the oracle's, and the decision of EVERY candidate pair (the predicate
+rows of the production run, LdPruneEngine.last_pred) with the float64 reference of ldtools (band_pair_stats / band_decisions).  Prints
+the first mismatching case (seed) and exits non-zero.
+    python tests/fuzz_parity.py [--cases 150] [--seed 1] [--mixed | --wide-missing | --wide-sparse | --wide-async]"""
 import argparse
 import os
 import sys
@@ -18,7 +20,7 @@ import ldtools as T  # noqa: E402
 import __graft_entry__ as ge  # noqa: E402
 
 
-def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=False):
+def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=False, mixed=False):
     n = int(rng.choice([33, 64, 100, 511, 512, 513, 1000, 1536, 2047, 2049, 3000, 5000, 9000]))
     if wide_sparse:
         n = int(rng.choice([1536, 2049, 5000, 9000, 20000, 40000]))   # --wide-sparse: enough 512-sample stages for the checkpoints to fire
@@ -30,7 +32,19 @@ def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=Fa
         miss = 0.0                                    # --wide-async: complete data through the tile plan on the barrier-free kernel
     if wide_missing:
         miss = float(rng.choice([0.01, 0.05, 0.2]))   # --wide-missing: every case on the missing-call kernels ...
-    raw = T.synth_raw_codes(m, n, seed=int(rng.integers(1, 1 << 30)), missing_rate=miss)
+    raw = T.synth_raw_codes(m, n, seed=int(rng.integers(1, 1 << 30)), missing_rate=0.0 if mixed else miss)
+    if mixed:
+        # --mixed: the rows' missing rate is drawn per block of rows from {0, 0.1 %, 5 %} (a generator of its own, so that the sequence of the
+        # other modes' cases stays what it was): complete stretches next to incomplete ones, the route following whatever is resident
+        mrng = np.random.default_rng(int(rng.integers(1, 1 << 30)))
+        a = 0
+        while a < m:
+            b = min(m, a + int(mrng.integers(8, max(9, m // 2))))
+            rate = float(mrng.choice([0.0, 0.001, 0.05]))
+            if rate:
+                raw[a:b] = np.where(mrng.random((b - a, n)) < rate, 3, raw[a:b])
+            a = b
+        miss = float((raw == 3).mean())
     # sprinkle structure: copies with noise (LD), monomorphic rows, an all-missing row, rare variants
     for _ in range(m // 6):
         a = int(rng.integers(1, m))
@@ -86,12 +100,19 @@ def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=Fa
             eng.load_genotypes_host(a, packed[a:b], pkg.LDP_GENO_REF)
     got = eng.run()
     ctr = eng.counters()
+    pred, outside = eng.last_pred(with_outside=True)
+    lo, _ = eng.band()
     eng.close()
-    ok = np.array_equal(got, want)
-    desc = "case %d: n=%d m=%d miss=%g %s window=%d step=%d r2=%g order=%d chr=%d wide_min_reach=%d tiles=%d four_tile_launches=%d sparse_tile_launches=%d recounted=%d removed=%d skipped=%.2f" % (
+    # every candidate pair's decision of this (production) run against the float64 reference
+    stats = T.band_pair_stats(raw, lo)
+    pairs_wrong, pair_msg = T.compare_decisions(pred, T.band_decisions(stats, r2), lo, stats, r2, counters=ctr, limit=3)
+    ok = np.array_equal(got, want) and (pairs_wrong == 0) and (outside == 0) and (int(pred.sum()) == ctr["pred_true"])
+    desc = "case %d: n=%d m=%d miss=%g %s window=%d step=%d r2=%g order=%d chr=%d wide_min_reach=%d tiles=%d four_tile_launches=%d sparse_tile_launches=%d recounted=%d removed=%d skipped=%.2f pairs=%d pairs_wrong=%d outside_band=%d" % (
         idx, n, m, miss, "bp" if is_bp else "count", window, step, r2, order, n_chr, wide, ctr["wide_tiles"], ctr["four_tile_launches"], ctr["sparse_tile_launches"],
         ctr["sparse_exact_pairs"], int(want.sum()),
-        (ctr["mfma_skipped_product_stages"] / ctr["mfma_product_stages"]) if ctr["mfma_product_stages"] else 0.0)
+        (ctr["mfma_skipped_product_stages"] / ctr["mfma_product_stages"]) if ctr["mfma_product_stages"] else 0.0, len(pred), pairs_wrong, outside)
+    if pairs_wrong:
+        desc += "\n" + pair_msg
     return ok, desc
 
 
@@ -100,15 +121,16 @@ def main():
     ap.add_argument("--cases", type=int, default=150)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--wide-missing", action="store_true", help="every case has missing calls and takes the wide-band tile plan (pair_mfma_tile4_kernel)")
-    ap.add_argument("--wide-sparse", action="store_true", help="every case has a FEW missing calls (0.01-0.5 %) and takes the tile plan: pair_mfma_wide_kernel's SPARSE instantiation")
+    ap.add_argument("--wide-sparse", action="store_true", help="every case has a FEW missing calls (0.01-0.5 %%) and takes the tile plan: pair_mfma_wide_kernel's SPARSE instantiation")
     ap.add_argument("--wide-async", action="store_true", help="every case is complete data on the tile plan, run by pair_mfma_wide_async_kernel (engine option wide_async)")
+    ap.add_argument("--mixed", action="store_true", help="the rows' missing rate is drawn per block of rows from {0, 0.1 %%, 5 %%}: mixed-missingness filesets")
     args = ap.parse_args()
     pkg = ge.load_package()
     rng = np.random.default_rng(args.seed)
     t0 = time.time()
     skipped_any = sparse_tiles = 0
     for k in range(args.cases):
-        ok, desc = one_case(pkg, rng, k, args.wide_missing, args.wide_async, args.wide_sparse)
+        ok, desc = one_case(pkg, rng, k, args.wide_missing, args.wide_async, args.wide_sparse, args.mixed)
         if "skipped=0.00" not in desc:
             skipped_any += 1
         if "sparse_tile_launches=0" not in desc:

@@ -725,3 +725,109 @@ def add_pgen_header_extension(pgen_path, out_path, writer_id=b"ldtools test writ
         hdr[12 + 8 * b:20 + 8 * b] = (o + len(ext)).to_bytes(8, "little")
     with open(out_path, "wb") as f:
         f.write(bytes(hdr) + ext + data[header_len:])
+
+
+# ---------------------------------------------------------------- every candidate pair of a band, by plain matrix products
+PAIR_FIELDS = ("nm", "sum1", "ssq1", "sum2", "ssq2", "dot")
+
+
+def band_pairs(lo):
+    """(first, second) int64 index arrays of every candidate pair of a band, in the order of ldp_run_with_stats()'s stats
+    array: second variant ascending, first variant from lo[second] to second - 1."""
+    lo = np.asarray(lo, dtype=np.int64)
+    m = len(lo)
+    j = np.arange(m, dtype=np.int64)
+    cnt = np.maximum(j - lo, 0)
+    second = np.repeat(j, cnt)
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    first = np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1] - lo, cnt)
+    return first, second
+
+
+def band_pair_stats(raw, lo, block=256):
+    """The six integers (nm, sum1, ssq1, sum2, ssq2, dot) of EVERY candidate pair (i, j), lo[j] <= i < j, as a (pairs, 6) int64
+    array in band order (band_pairs).  raw: REF-based codes (M, N); every variant is oriented on its major allele (REF unless
+    ref_ct * (1 / total) < 0.5, the definition of plink2_common.h:559-567; an exact tie goes to REF), x = +1 hom-major, 0 het,
+    -1 hom-minor, and the sums run over the samples both variants have a call for.  Plain float64 matrix products of the
+    three indicator / valued matrices (call present, homozygous, x): every sum is an integer far below 2^53, so the products
+    are exact whatever order BLAS adds in.  Shares no code with oracle/ldoracle.c or with the kernels."""
+    raw = np.asarray(raw)
+    lo = np.asarray(lo, dtype=np.int64)
+    m, n = raw.shape
+    n_ref = (raw == 0).sum(1).astype(np.int64)
+    n_het = (raw == 1).sum(1).astype(np.int64)
+    n_alt = (raw == 2).sum(1).astype(np.int64)
+    ref_ct = 2 * n_ref + n_het
+    tot = ref_ct + 2 * n_alt + n_het
+    ref_freq = np.where(tot > 0, ref_ct.astype(np.float64) * (1.0 / np.maximum(tot, 1).astype(np.float64)), 0.5)
+    sign = np.where(ref_freq >= 0.5, 1.0, -1.0)
+    C = (raw != 3).astype(np.float64)
+    H = ((raw == 0) | (raw == 2)).astype(np.float64)
+    X = ((raw == 0).astype(np.float64) - (raw == 2).astype(np.float64)) * sign[:, None]
+    cnt = np.maximum(np.arange(m, dtype=np.int64) - lo, 0)
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    out = np.zeros((int(off[-1]), 6), dtype=np.int64)
+    for j0 in range(0, m, block):
+        j1 = min(m, j0 + block)
+        if off[j1] == off[j0]:
+            continue
+        i0 = int(min(lo[j0:j1].min(), j0))
+        Ci, Hi, Xi = C[i0:j1], H[i0:j1], X[i0:j1]
+        CjT, HjT, XjT = C[j0:j1].T, H[j0:j1].T, X[j0:j1].T
+        prods = (Ci @ CjT, Xi @ CjT, Hi @ CjT, Ci @ XjT, Ci @ HjT, Xi @ XjT)   # [i - i0, j - j0]
+        for j in range(j0, j1):
+            if cnt[j]:
+                a, b = int(lo[j]) - i0, j - i0
+                for f in range(6):
+                    out[off[j]:off[j + 1], f] = np.rint(prods[f][a:b, j - j0]).astype(np.int64)
+    return out
+
+
+def _stats_columns(stats):
+    stats = np.asarray(stats)
+    if stats.dtype.names:
+        return [stats[f].astype(np.int64) for f in PAIR_FIELDS]
+    return [stats[:, f].astype(np.int64) for f in range(6)]
+
+
+def band_cov_vars(stats):
+    """(cov12, var1, var2) as float64 arrays: the integer parts in int64 (plink2_ld.cc:1085-1087), then one conversion each."""
+    nm, s1, q1, s2, q2, dot = _stats_columns(stats)
+    return (dot * nm - s1 * s2).astype(np.float64), (q1 * nm - s1 * s1).astype(np.float64), (q2 * nm - s2 * s2).astype(np.float64)
+
+
+def band_decisions(stats, r2):
+    """The prune predicate of every pair: cov * cov > (thr * var1) * var2 with thr = ldo_prune_thresh(r2), three float64
+    multiplications in exactly that order, var1 the FIRST variant's (plink2_ld.cc:1085-1090; numpy's elementwise products are
+    separate roundings, nothing is contracted).  stats: (pairs, 6) integers or a structured array with PAIR_FIELDS."""
+    thr = float(oracle().ldo_prune_thresh(float(r2)))
+    cov, v1, v2 = band_cov_vars(stats)
+    return (cov * cov) > ((thr * v1) * v2)
+
+
+def compare_decisions(got, want, lo, stats, r2, counters=None, limit=10):
+    """Per-pair comparison of two decision arrays in band order: (number of differing pairs, message).  The message names the
+    first `limit` differing pairs (i, j) with their six integers, cov^2 / (thr var1 var2) and, when given, the route counters
+    of the run, so that a failure says whether it is a bound, an ownership error or arithmetic."""
+    got = np.asarray(got, dtype=bool)
+    want = np.asarray(want, dtype=bool)
+    if got.shape != want.shape:
+        return max(len(got), len(want)), "decision arrays differ in length: %d vs %d" % (len(got), len(want))
+    bad = np.flatnonzero(got != want)
+    if not len(bad):
+        return 0, "all %d pairs agree" % len(got)
+    first, second = band_pairs(lo)
+    thr = float(oracle().ldo_prune_thresh(float(r2)))
+    cols = _stats_columns(stats)
+    cov, v1, v2 = band_cov_vars(stats)
+    lines = ["%d of %d pairs differ (got %d true, want %d true)" % (len(bad), len(got), int(got.sum()), int(want.sum()))]
+    for k in bad[:limit]:
+        den = (thr * v1[k]) * v2[k]
+        ratio = (cov[k] * cov[k]) / den if den != 0 else float("nan")
+        lines.append("  pair (i=%d, j=%d): got %d want %d; nm,sum1,ssq1,sum2,ssq2,dot = %s; cov^2/(thr var1 var2) = %.17g"
+                     % (first[k], second[k], int(got[k]), int(want[k]), tuple(int(c[k]) for c in cols), ratio))
+    if counters is not None:
+        keys = ("pair_kernel_launches", "route_complete_launches", "route_sparse_launches", "route_general_launches", "sparse_tile_launches",
+                "four_tile_launches", "wide_tiles", "mfma_skipped_product_stages", "sparse_exact_pairs", "pred_true")
+        lines.append("  counters: " + ", ".join("%s=%s" % (k, counters[k]) for k in keys if k in counters))
+    return len(bad), "\n".join(lines)

@@ -1,0 +1,157 @@
+"""CPU tests of the per-pair reference the GPU tests compare the production kernels' decisions with (ldtools.band_pair_stats,
+band_decisions, compare_decisions): plain float64 matrix products and three float64 multiplications, checked here against
+the oracle's word-by-word popcount arithmetic (oracle/ldoracle.c) for EVERY candidate pair of small bands that hold the rows
+kernels go wrong on.  Also the measurement of how much of a single wrong decision the prune set shows."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import ldtools as T
+from test_host_logic import make_positions, recs_from_vaggs
+
+
+def edge_rows(m, n, seed):
+    """complete rows, rows at 0.1 % / 5 % / 70 % missing, the four monomorphic kinds, an exact REF = ALT tie, ALT-major rows"""
+    rng = np.random.default_rng(seed)
+    raw = T.synth_raw_codes(m, n, seed, missing_rate=0.0, ld_copy_prob=0.6, redraw=0.1)
+    for v in range(m):
+        rate = (0.0, 0.001, 0.05, 0.7)[v % 4]
+        if rate:
+            raw[v, rng.random(n) < rate] = 3
+    raw[3] = 0                      # monomorphic hom-REF
+    raw[9] = 2                      # monomorphic hom-ALT
+    raw[14] = 1                     # all het
+    raw[20] = 3                     # all missing
+    raw[26] = 0
+    raw[26, : n // 2] = 2           # ref_ct == alt_ct when n is even: the tie goes to REF
+    for v in (5, 11, 12, 30):       # ALT is the major allele
+        raw[v] = np.where(rng.random(n) < 0.8, 2, rng.integers(0, 2, size=n))
+        raw[v, rng.random(n) < 0.02] = 3
+    return raw
+
+
+def oracle_all_pairs(raw, lo, r2):
+    m, n = raw.shape
+    inv, mf, altmaj = T.oracle_prepare(raw)
+    hom, r2h, vaggs = T.oracle_split(inv, n)
+    lib = T.oracle()
+    thr = lib.ldo_prune_thresh(r2)
+    stats, dec = [], []
+    for j in range(m):
+        for i in range(int(lo[j]), j):
+            st = T.oracle_pair_stats(hom, r2h, vaggs, n, i, j)
+            stats.append(st.astuple())
+            dec.append(bool(lib.ldo_exceeds(ctypes.byref(st), thr)))
+    return np.array(stats, dtype=np.int64).reshape(-1, 6), np.array(dec, dtype=bool), altmaj
+
+
+@pytest.mark.parametrize("n", [2, 63, 64, 65, 1025])
+@pytest.mark.parametrize("is_bp,window", [(False, 25), (True, 6000)])
+def test_every_pair_of_a_band_equals_the_oracle(pkg, n, is_bp, window):
+    m = 64
+    raw = edge_rows(m, n, seed=100 + n)
+    chr_idx, bps = make_positions(m, 2, n + 3)
+    eng = pkg.LdPruneEngine(n, window, 1, is_bp, 0.2)
+    eng.set_variants(chr_idx, bps)
+    lo, cand = eng.band()
+    eng.close()
+    first, second = T.band_pairs(lo)
+    assert len(first) == cand > 300
+    k = 0
+    for j in range(m):                               # band_pairs is the order of ldp_run_with_stats()
+        for i in range(int(lo[j]), j):
+            assert (first[k], second[k]) == (i, j)
+            k += 1
+    stats = T.band_pair_stats(raw, lo, block=7)      # (a block size that cuts the band everywhere)
+    assert np.array_equal(stats, T.band_pair_stats(raw, lo))
+    for r2 in (0.02, 0.2, 0.5, 0.95):
+        want_stats, want_dec, altmaj = oracle_all_pairs(raw, lo, r2)
+        assert np.array_equal(stats, want_stats), np.flatnonzero((stats != want_stats).any(1))[:5]
+        got = T.band_decisions(stats, r2)
+        nd, msg = T.compare_decisions(got, want_dec, lo, stats, r2)
+        assert nd == 0, msg
+    assert altmaj[[5, 11, 12, 30]].all() or n == 2
+    assert not altmaj[26]
+    print("pairs compared: %d x 4 thresholds" % cand)
+
+
+def test_decisions_from_a_structured_stats_array(pkg):
+    """band_decisions takes the device's own tuples (ldp_pair_stats_t) as well"""
+    raw = edge_rows(40, 130, seed=5)
+    lo = np.maximum(np.arange(40) - 12, 0)
+    stats = T.band_pair_stats(raw, lo)
+    rec = np.zeros(len(stats), dtype=pkg.PAIR_STATS_DTYPE)
+    for f, name in enumerate(T.PAIR_FIELDS):
+        rec[name] = stats[:, f]
+    assert np.array_equal(T.band_decisions(rec, 0.3), T.band_decisions(stats, 0.3))
+    assert 0 < T.band_decisions(stats, 0.3).sum() < len(stats)
+
+
+def test_a_planted_one_bit_difference_is_named():
+    m, n = 50, 200
+    raw = T.synth_raw_codes(m, n, 9, missing_rate=0.02, ld_copy_prob=0.7, redraw=0.1)
+    lo = np.maximum(np.arange(m) - 9, 0)
+    stats = T.band_pair_stats(raw, lo)
+    want = T.band_decisions(stats, 0.2)
+    assert T.compare_decisions(want, want, lo, stats, 0.2)[0] == 0
+    first, second = T.band_pairs(lo)
+    k = int(np.flatnonzero((first == 30) & (second == 37))[0])
+    got = want.copy()
+    got[k] = not got[k]
+    nd, msg = T.compare_decisions(got, want, lo, stats, 0.2, counters={"pred_true": 7, "route_sparse_launches": 1})
+    assert nd == 1
+    assert "pair (i=30, j=37)" in msg and "got %d want %d" % (int(got[k]), int(want[k])) in msg
+    assert str(tuple(int(x) for x in stats[k])) in msg and "route_sparse_launches=1" in msg
+    # a second one: both are listed, in band order
+    got[0] = not got[0]
+    nd, msg = T.compare_decisions(got, want, lo, stats, 0.2)
+    assert nd == 2 and msg.index("pair (i=0, j=1)") < msg.index("pair (i=30, j=37)")
+    assert T.compare_decisions(got[:-1], want, lo, stats, 0.2)[0] > 0
+
+
+SENSITIVITY_SHAPES = [
+    # m, n, window (variants), r2, missing
+    (1500, 3000, 600, 0.2, 0.001),
+    (700, 2000, 150, 0.5, 0.05),
+]
+
+
+@pytest.mark.parametrize("shape", SENSITIVITY_SHAPES)
+def test_how_much_of_one_wrong_decision_the_prune_set_shows(pkg, shape):
+    """A measurement kept reproducible, not a bound: the reference's decisions of every candidate pair go through the greedy scan
+    (ldp_debug_replay_pairs) with ONE decision changed at a time, 400 times a true one dropped and 400 times a false one set, and
+    the number of trials in which the prune set changes is printed (DESIGN 5a has the table).  The scan ignores a pair as soon as
+    one of its variants is gone, so most single errors leave the set as it was: that is why the GPU tests compare the
+    predicate rows themselves (tests/test_pair_decisions.py)."""
+    m, n, window, r2, miss = shape
+    trials = 400
+    raw = T.synth_raw_codes(m, n, seed=m + n, missing_rate=miss, ld_copy_prob=0.5, redraw=0.05)
+    chr_idx = np.zeros(m, dtype=np.uint32)
+    inv, mf, _ = T.oracle_prepare(raw)
+    _, _, vaggs = T.oracle_split(inv, n)
+    eng = pkg.LdPruneEngine(n, window, 1, False, r2)
+    eng.set_variants(chr_idx, None)
+    lo, cand = eng.band()
+    eng.debug_set_variant_recs(recs_from_vaggs(pkg, vaggs, n, m))
+    eng.set_maj_freqs(0, mf)
+    dec = T.band_decisions(T.band_pair_stats(raw, lo), r2)
+    first, second = T.band_pairs(lo)
+    first, second = first.astype(np.uint32), second.astype(np.uint32)
+    base = eng.debug_replay_pairs(first[dec], second[dec])
+    want, _ = T.oracle_indep_pairwise(inv, n, chr_idx, np.arange(m, dtype=np.uint32), mf, window, 1, False, r2, 2)
+    assert np.array_equal(base, want)
+    rng = np.random.default_rng(7)
+    true_idx, false_idx = np.flatnonzero(dec), np.flatnonzero(~dec)
+    changed = {}
+    for name, pool in (("one TRUE decision dropped", true_idx), ("one FALSE decision set", false_idx)):
+        changed[name] = 0
+        for k in rng.choice(pool, size=trials, replace=False):
+            d = dec.copy()
+            d[k] = not d[k]
+            changed[name] += int(not np.array_equal(eng.debug_replay_pairs(first[d], second[d]), base))
+    eng.close()
+    print("sensitivity m=%d n=%d window=%d r2=%g missing=%g: %d true of %d candidates; %s"
+          % (m, n, window, r2, miss, len(true_idx), cand, "; ".join("%s: set changed in %d of %d" % (k, v, trials) for k, v in changed.items())))
+    for v in changed.values():
+        assert v < trials
