@@ -80,6 +80,12 @@ int ldp_debug_mfma_plan(const ldp_engine* e, uint32_t* wg_count, uint32_t* words
  * leave those to the tiles.  words == NULL only counts. */
 int ldp_debug_wide_plan(const ldp_engine* e, uint32_t* tile_count, uint32_t* words, uint64_t capacity_words);
 
+/* The wave -> rectangle map of the DIAGONAL tiles' 2 x 3 body ("wide_diag_kernel"; csrc/ldp_device.h: kWdDiagMap, the table the kernel's
+ * constants are made from), no engine and no GPU needed.  Per wave (eight of them; waves w and w + 4 share a SIMD) 5 words: a0, b0 (the
+ * rectangle: J blocks a0, a0 + 1 x V blocks b0 .. b0 + 2), cols (bit b: the wave owns the products of V block b0 + b), then the products
+ * it owns as mask bits 0-31 / 32-63 in ldp_debug_wide_plan()'s layout (bit 8 a + b).  capacity_words < 40: LDP_ERR_INVALID. */
+int ldp_debug_wide_diag_map(uint32_t* words, uint64_t capacity_words);
+
 
 /* ---- synthetic workload (benchmark / test support, not part of the reference seam) ---- */
 /* Deterministic genotype generator for the SURVEY.md 8(d) workload: rows [first_variant, +n_variants) of

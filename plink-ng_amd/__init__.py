@@ -101,7 +101,7 @@ CABI_SYMBOLS = [
     "ldp_pgen_variant_is_multiallelic", "ldp_pgen_provisional_ref", "ldp_pgen_open_indexed", "ldp_set_r_signed", "ldp_set_variants_vcor_cm", "ldp_pgen_read_alleles", "ldp_pgen_read_phased", "ldp_pgen_read_alleles_phased", "ldp_subset_samples", "ldp_phased_row_bytes", "ldp_phased_phase_offset",
     "ldp_debug_set_option", "ldp_pgen_debug_force_portable", "ldp_matrix_pipe_max_founders", "ldp_map_rows", "ldp_release_device", "ldp_debug_wide_plan",
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
-    "ldp_use_private_copy_threads", "ldp_debug_get_pred",
+    "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map",
 ]
 
 
@@ -236,6 +236,7 @@ def lib():
     L.ldp_comm_destroy.argtypes = [vp]
     L.ldp_comm_destroy.restype = None
     L.ldp_debug_wide_plan.argtypes = [vp, u32p, u32p, ctypes.c_uint64]
+    L.ldp_debug_wide_diag_map.argtypes = [u32p, ctypes.c_uint64]
     L.ldp_matrix_pipe_max_founders.argtypes = []
     L.ldp_matrix_pipe_max_founders.restype = ctypes.c_uint32
     L.ldp_debug_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_double]
@@ -857,6 +858,16 @@ class LdPruneEngine:
         words = np.zeros((max(n.value, 1), 5), dtype=np.uint32)
         self._ck(self._L.ldp_debug_wide_plan(self._h, ctypes.byref(n), _ptr(words, ctypes.c_uint32), words.size))
         return words[:n.value]
+
+    @staticmethod
+    def debug_wide_diag_map():
+        """the diagonal tiles' wave -> rectangle map as an (8, 5) uint32 array: a0, b0, owned columns, owned products' mask low / high word
+        (ldp_debug_wide_diag_map; the kernel's own table, no GPU needed)."""
+        words = np.zeros((8, 5), dtype=np.uint32)
+        rc = lib().ldp_debug_wide_diag_map(_ptr(words, ctypes.c_uint32), words.size)
+        if rc != LDP_OK:
+            raise LdpError(rc, "ldp_debug_wide_diag_map")
+        return words
 
     # ---- inspection
     def variant_recs(self, first=0, n=None):

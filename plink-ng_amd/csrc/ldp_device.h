@@ -135,6 +135,74 @@ constexpr int kWdWaves = 8;
 constexpr int kWdTile = 8;                       // row-blocks per tile side
 constexpr int kWdRowBlocks = 2 * kWdTile;        // staged row-blocks: slots 0..7 the J blocks, 8..15 the V blocks
 constexpr uint32_t kWdMinReach = 12;             // a subcontig whose band reaches this many row-blocks takes the wide plan
+
+// The wave -> rectangle map of DIAGONAL tiles (pair_mfma_wide_kernel's 2 x 3 body, ldp_pair_wide.hip; PairKernelArgs::wd_diag_split): wave w multiplies
+// J blocks a0, a0 + 1 with V blocks b0 .. b0 + 2 and OWNS the products of the columns in `cols` (bit b: V block b0 + b) that lie on or below the
+// diagonal (V block <= J block).  A product of its rectangle a wave does not own is computed and never live -- never decided, never written: a
+// product "beyond the plan".  Waves 0-3 ("near") hold every product on and next to the block diagonal, (j, j) and (j, j - 1): the only ones that
+// can still hold a pair in LD once a checkpoint has dropped the distant ones, so the tail of a diagonal tile runs on one wave per SIMD (waves w and
+// w + 4 share a SIMD).  Waves 4-7 ("rest") hold the products at least two blocks off the diagonal; (2,0) / (2,1) and (6,3) / (6,5) overlap in a
+// column, hence `cols`.  Wave w + 4 reads the J blocks of wave w where the triangle allows (rows 6-7 have two rest rectangles, rows 0-1 none).
+// The ONE definition: the kernel packs its constants from this table, ldp_debug_wide_diag_map() hands it to the tests.
+struct WdDiagRect {
+  uint8_t a0, b0, cols;
+};
+constexpr int kWdDiagCols = 3;
+constexpr WdDiagRect kWdDiagMap[kWdWaves] = {{0, 0, 7}, {2, 1, 7}, {4, 3, 7}, {6, 5, 7}, {6, 3, 3}, {2, 0, 1}, {4, 0, 7}, {6, 0, 7}};
+// products wave w owns (bit 8 j + v: J block j, V block v -- MfmaTile::mask's layout)
+constexpr uint64_t wd_diag_owned(int w) {
+  uint64_t m = 0;
+  for (int q = 0; q < 2; ++q) {
+    for (int b = 0; b < kWdDiagCols; ++b) {
+      const int j = kWdDiagMap[w].a0 + q, v = kWdDiagMap[w].b0 + b;
+      if (((kWdDiagMap[w].cols >> b) & 1) && (v <= j)) {
+        m |= 1ull << (8 * j + v);
+      }
+    }
+  }
+  return m;
+}
+// field 0 / 1 / 2 = a0 / b0 / cols of wave w in bits 4 w .. 4 w + 3 (the kernel's compile-time constants)
+constexpr uint32_t wd_diag_packed(int field) {
+  uint32_t p = 0;
+  for (int w = 0; w < kWdWaves; ++w) {
+    const uint32_t x = (field == 0) ? kWdDiagMap[w].a0 : ((field == 1) ? kWdDiagMap[w].b0 : kWdDiagMap[w].cols);
+    p |= x << (4 * w);
+  }
+  return p;
+}
+constexpr bool wd_diag_partitions() {
+  uint64_t all = 0, want = 0;
+  for (int w = 0; w < kWdWaves; ++w) {
+    const uint64_t m = wd_diag_owned(w);
+    if ((all & m) || (kWdDiagMap[w].a0 + 1 >= kWdTile) || (kWdDiagMap[w].b0 + kWdDiagCols > kWdTile) || (kWdDiagMap[w].cols >> kWdDiagCols)) {
+      return false;  // a product owned twice, or a rectangle that leaves the tile
+    }
+    all |= m;
+  }
+  for (int j = 0; j < kWdTile; ++j) {
+    for (int v = 0; v <= j; ++v) {
+      want |= 1ull << (8 * j + v);
+    }
+  }
+  return all == want;
+}
+constexpr bool wd_diag_near_on_four_waves() {
+  uint64_t near = 0;
+  for (int w = 0; w < 4; ++w) {
+    near |= wd_diag_owned(w);
+  }
+  for (int j = 0; j < kWdTile; ++j) {
+    for (int v = (j ? j - 1 : 0); v <= j; ++v) {
+      if (!((near >> (8 * j + v)) & 1)) {
+        return false;
+      }
+    }
+  }
+  return true;
+}
+static_assert(wd_diag_partitions(), "the eight owned sets partition the 36 products with v <= j exactly");
+static_assert(wd_diag_near_on_four_waves(), "waves 0-3 own every (j, j) and (j, j - 1)");
 struct MfmaTile {
   int32_t jv;        // first variant of J block 0 (J block a = jv + 32 a)
   int32_t vv;        // first variant of V block 0 (V block b = vv + 32 b); == jv on the diagonal
@@ -210,8 +278,8 @@ struct PairKernelArgs {
   uint32_t wd_async;             // the tiles run on pair_mfma_wide_async_kernel (no workgroup barrier in the stage loop; EngineOptions::wide_async)
   uint32_t wd_sparse;            // the tiles also own the launch on the kRouteSparse route (pair_mfma_wide_kernel<., SPARSE>; EngineOptions::wide_sparse):
                                  // pair_mfma_kernel<., SPARSE = true> then skips the workgroups of their subcontigs as the complete-data kernel does
-  uint32_t wd_diag_split;        // complete-data prune launches: the tiles on the diagonal are left to pair_mfma_wide_kernel<., false, 3> (2 x 3 rectangles on all eight
-                                 // waves), queued behind the 2 x 4 kernel (EngineOptions::wide_diag_kernel)
+  uint32_t wd_diag_split;        // complete-data prune launches: the tiles on the diagonal take the kernel's 2 x 3 body (kWdDiagMap: 2 x 3 rectangles on all eight
+                                 // waves), picked per workgroup (EngineOptions::wide_diag_kernel)
 };
 
 constexpr uint32_t kRouteComplete = 0, kRouteSparse = 1, kRouteGeneral = 2;

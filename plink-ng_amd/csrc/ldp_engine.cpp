@@ -827,11 +827,15 @@ void build_shard(ldp_engine* e) {
     // by J tile, and the tiles next to the diagonal at the end -- the diagonal ones and their first neighbours, which hold the rest
     // of the pairs in LD (config 3's share, kernel ms with the last 0 / 1 / 2 / 3 / 4 tile distances deferred: 330 / 302 / 296 / 297 /
     // 319; HBM traffic 6.1 -> 5.3 x compulsory with 1).  Streams are padded to equal length with empty tiles (mask 0).
-    // the diagonal tiles' own kernel covers J blocks (0,1) x V 0-2, (2,3) and (4,5) x V 0-5, (6,7) x V 0-7: every prune plan's diagonal tile lies
-    // inside (its live products are on and below the diagonal); a plan that does not keeps the 2 x 4 kernel for them
+    // the diagonal tiles' own body owns the 36 products on and below the diagonal (kWdDiagMap, ldp_device.h): every prune plan's diagonal tile lies
+    // inside; a plan that does not keeps the 2 x 4 body for them
+    uint64_t diag_owned = 0;
+    for (int w = 0; w < kWdWaves; ++w) {
+      diag_owned |= wd_diag_owned(w);
+    }
     e->wd_diag_lower = !e->wd_tiles.empty();
     for (const MfmaTile& t : e->wd_tiles) {
-      if ((t.jv == t.vv) && (t.mask & ~0xffff3f3f3f3f0707ull)) {
+      if ((t.jv == t.vv) && (t.mask & ~diag_owned)) {
         e->wd_diag_lower = false;
       }
     }
@@ -1728,6 +1732,21 @@ int ldp_debug_wide_plan(const ldp_engine* e, uint32_t* tile_count, uint32_t* wor
     *words++ = t.jend;
     *words++ = static_cast<uint32_t>(t.mask);
     *words++ = static_cast<uint32_t>(t.mask >> 32);
+  }
+  return LDP_OK;
+}
+
+int ldp_debug_wide_diag_map(uint32_t* words, uint64_t capacity_words) {
+  if (!words || (capacity_words < 5ull * kWdWaves)) {
+    return LDP_ERR_INVALID;
+  }
+  for (int w = 0; w < kWdWaves; ++w) {
+    const uint64_t owned = wd_diag_owned(w);
+    *words++ = kWdDiagMap[w].a0;
+    *words++ = kWdDiagMap[w].b0;
+    *words++ = kWdDiagMap[w].cols;
+    *words++ = static_cast<uint32_t>(owned);
+    *words++ = static_cast<uint32_t>(owned >> 32);
   }
   return LDP_OK;
 }

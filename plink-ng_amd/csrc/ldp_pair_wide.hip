@@ -244,8 +244,11 @@ __device__ __forceinline__ void wide_stage_kept(mf_u4 H, mf_u4 R, mf_v16f (&acc)
 // what the waves of the measured launches spent where (shader cycles, summed over waves; ABL bit 5 fills 0-5 and 9-10, every measured
 // instantiation 6-8): [0] s_waitcnt vmcnt in front of the stage barrier, [1] the stage barrier itself, [2] stages of waves with a live
 // product (DMA issue + LDS reads + expansions + MFMA issue), [3] stages of waves with none, [4] checkpoints, [5] epilogue, [6] entry to
-// exit, [7] waves, [8] entry to exit in 100 MHz wall ticks (shader clock = 100 MHz x [6] / [8]), [9] / [10] stage visits live / dead
-__device__ unsigned long long g_wide_measure[16];
+// exit, [7] waves, [8] entry to exit in 100 MHz wall ticks (shader clock = 100 MHz x [6] / [8]), [9] / [10] stage visits live / dead;
+// [11]-[13] the barrier-free kernel's; the barrier kernel's tiles ON the diagonal: [16] tiles, [17] stages they ran (one per tile and stage), [18] of those with at
+// most four waves live, [19] with exactly one, [20 + s] stages a wave of SIMD s (waves s and s + 4) ran live; the same for the tiles ONE tile distance from the
+// diagonal in [24]-[27], and [28] how many of those ran some stage on exactly one live wave
+__device__ unsigned long long g_wide_measure[32];
 __device__ __forceinline__ unsigned long long wd_clk() {
   __builtin_amdgcn_sched_barrier(0);
   const unsigned long long t = __builtin_readcyclecounter();
@@ -340,8 +343,13 @@ __device__ __forceinline__ uint32_t wide_sparse_round(const PairKernelArgs& A, c
 // VC == 3: the body for DIAGONAL tiles (PairKernelArgs::wd_diag_split; complete data, prune launches; round 6).  A diagonal tile holds 36 live
 // products -- those on and below the diagonal -- and runs to the end of the rows (the pairs in LD are there): with 2 x 4 rectangles six waves
 // compute 48 products at eight per wave while two have nothing to do, and the tile takes as long as a full one.  Here the same triangle is cut
-// into eight 2 x 3 rectangles -- J blocks (0,1) x V 0-2, (2,3) x V 0-2 | 3-5, (4,5) x V 0-2 | 3-5, (6,7) x V 0-2 | 3-5 | 6-7 -- 48 products again,
-// but six per wave on all eight waves: three quarters of the matrix-pipe time per stage.  Everything else is the code of the 2 x 4 body; the kernel
+// into eight 2 x 3 rectangles, 48 products again, but six per wave on all eight waves: three quarters of the matrix-pipe time per stage.  The cut
+// (kWdDiagMap, ldp_device.h) follows what the checkpoints leave: the products on and next to the block diagonal, (j, j) and (j, j - 1), are the ones
+// that run to the end of the rows, and they lie in the four NEAR rectangles (a0, b0) = (0,0) (2,1) (4,3) (6,5) on waves 0-3 -- one per SIMD; the 18
+// products two or more blocks off the diagonal belong to the REST rectangles (2,0) [column 0], (4,0), (6,0), (6,3) [columns 3-4] on waves 4-7, which
+// retire as whole waves once those are hopeless: the tail of a tile then runs on one wave per SIMD, six products each, instead of on six waves
+// spread over two full and two half SIMDs.  Rectangles overlap in a column ((2,0) / (2,1), (6,3) / (6,5)); a wave owns the columns of its `own`
+// constant, and a product it does not own is computed and never live, decided or written.  Everything else is the code of the 2 x 4 body; the kernel
 // picks one of the two per workgroup (block-uniform), so each body keeps its ONE form of the stage loop.  Measured (profiles/r06_experiments.md
 // section 4): as a launch of its own behind the others the diagonal tiles lose the L2 sharing with their neighbours (the share 339 against 273 ms
 // of pair kernels); inside the one launch 266.7 against 273.3 ms.  2 x 2 quads for tiles with at most eight live quads (the far tile of a J tile)
@@ -377,24 +385,36 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
   stages = (stages > kWdMaxStages) ? kWdMaxStages : stages;
 
   // ---- this wave's rectangle: J blocks a0, a0 + 1, V blocks b0 .. b0 + VC - 1 (product b: J block a0, V block b0 + b; VC + b: J block a0 + 1) ----
-  // VC == 3, wave 0 .. 7: (a0, b0) = (0,0) (2,0) (2,3) (4,0) (4,3) (6,0) (6,3) (6,6)
+  // VC == 3, wave 0 .. 7: kWdDiagMap (ldp_device.h) -- near rectangles (0,0) (2,1) (4,3) (6,5) on waves 0-3, the rest (6,3) (2,0) (4,0) (6,0) on waves 4-7; `own`:
+  // the columns of its rectangle whose products a wave owns ((2,0) owns column 0, (6,3) columns 3-4: the near rectangles hold the others).  A slot the wave
+  // does not own is a slot beyond the plan: computed, never live.
   // VC == 4, wave 0 .. 7: (a0, b0) = (0,0) (2,4) (4,0) (6,4) | (0,4) (2,0) (4,4) (6,0).  Waves w and w + 4 read the same two J blocks (as in rounds 2-5); since
   // round 6 neighbouring waves take different V halves.  Four maps, one library each, alternating on one box (profiles/r06_experiments.md 4b): this one
   // 272.5 ms of pair kernels per step of the share; b0 = 4 (w >> 2), the map of rounds 2-5, 275.0-275.8; waves w, w + 4 sharing their V blocks instead
   // 276.1-276.5; sharing nothing 277.2 against 271.8.
-  auto rect_a0 = [](uint32_t w) -> uint32_t { return ((VC == 4) ? (0x64206420u >> (4 * w)) : (0x66644220u >> (4 * w))) & 0xfu; };
-  auto rect_b0 = [](uint32_t w) -> uint32_t { return ((VC == 4) ? (0x04044040u >> (4 * w)) : (0x63030300u >> (4 * w))) & 0xfu; };
-  const uint32_t a0 = rect_a0(wave), b0 = rect_b0(wave);
+  static_assert(kWdDiagCols == 3, "the diagonal tiles' map is made for the 2 x 3 body");
+  constexpr uint32_t kDiagA0 = wd_diag_packed(0), kDiagB0 = wd_diag_packed(1), kDiagOwn = wd_diag_packed(2);  // (compile-time: a map read from memory made hipcc spill)
+  auto rect_a0 = [](uint32_t w) -> uint32_t { return ((VC == 4) ? (0x64206420u >> (4 * w)) : (kDiagA0 >> (4 * w))) & 0xfu; };
+  auto rect_b0 = [](uint32_t w) -> uint32_t { return ((VC == 4) ? (0x04044040u >> (4 * w)) : (kDiagB0 >> (4 * w))) & 0xfu; };
+  auto rect_own = [](uint32_t w) -> uint32_t { return (VC == 4) ? kColMask : ((kDiagOwn >> (4 * w)) & kColMask); };
+  const uint32_t a0 = rect_a0(wave), b0 = rect_b0(wave), own = rect_own(wave);
   const uint32_t vslot0 = (diag ? 0u : static_cast<uint32_t>(kWdTile)) + b0;
   auto mask_row = [&](uint32_t a) { return ((a < 4) ? (mask_lo >> (8 * a)) : (mask_hi >> (8 * (a - 4)))) & 0xffu; };
-  uint32_t live = ((mask_row(a0) >> b0) & kColMask) | (((mask_row(a0 + 1) >> b0) & kColMask) << VC);
+  uint32_t live = ((mask_row(a0) >> b0) & own) | (((mask_row(a0 + 1) >> b0) & own) << VC);
   live = __builtin_amdgcn_readfirstlane(live);
   // row-block slots the workgroup reads: the rectangles of the waves that own a live product
   uint32_t wg_need = 0;
+#ifdef LDP_MEASURE
+  uint32_t m_live_waves = 0;  // waves of the workgroup with a live product (uniform); [0] stages, [1] with <= 4 waves live, [2] with one, [3] this wave live
+  unsigned long long m_ws[4] = {0, 0, 0, 0};
+#endif
 #pragma unroll
   for (uint32_t w = 0; w < static_cast<uint32_t>(kWdWaves); ++w) {
     const uint32_t wa = rect_a0(w), wb = rect_b0(w);
-    const uint32_t wl = ((mask_row(wa) | mask_row(wa + 1)) >> wb) & kColMask;
+    const uint32_t wl = ((mask_row(wa) | mask_row(wa + 1)) >> wb) & rect_own(w);
+#ifdef LDP_MEASURE
+    m_live_waves += wl ? 1u : 0u;
+#endif
     wg_need |= wide_slots_needed<VC>(wl, wa, (diag ? 0u : static_cast<uint32_t>(kWdTile)) + wb);
   }
   wg_need = __builtin_amdgcn_readfirstlane(wg_need);
@@ -554,6 +574,10 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
         m_t[live ? 2 : 3] += wd_clk() - m_s0;
         m_visits[live ? 0 : 1] += 1;
       }
+      m_ws[0] += 1;
+      m_ws[1] += (m_live_waves <= 4) ? 1u : 0u;
+      m_ws[2] += (m_live_waves == 1) ? 1u : 0u;
+      m_ws[3] += live ? 1u : 0u;
 #endif
     }
     if (kc >= n_stages) {
@@ -709,9 +733,15 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
     }
     __syncthreads();
     uint32_t all_need = 0;
+#ifdef LDP_MEASURE
+    m_live_waves = 0;
+#endif
 #pragma unroll
     for (int w = 0; w < kWdWaves; ++w) {
       all_need |= s_need[w];
+#ifdef LDP_MEASURE
+      m_live_waves += __builtin_amdgcn_readfirstlane(s_need[w] ? 1u : 0u);  // (a live wave needs its rectangle's row-blocks)
+#endif
     }
     __syncthreads();  // (s_need is rewritten at the next checkpoint; the scratch reads above are over as well)
     if (!all_need) {
@@ -829,6 +859,23 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
       atomicAdd(&g_wide_measure[6], m_clk1 - m_clk0);
       atomicAdd(&g_wide_measure[7], 1ull);
       atomicAdd(&g_wide_measure[8], m_wall1 - m_wall0);
+      // the tiles on the diagonal and their first neighbours: how many waves their stages ran on
+      const bool dist1 = (jv0 - vv0 == static_cast<int32_t>(kMfBlock * kWdTile));
+      if (diag || dist1) {
+        const int base = diag ? 16 : 24;
+        if (wave == 0) {
+          atomicAdd(&g_wide_measure[base], 1ull);
+          atomicAdd(&g_wide_measure[base + 1], m_ws[0]);
+          atomicAdd(&g_wide_measure[base + 2], m_ws[1]);
+          atomicAdd(&g_wide_measure[base + 3], m_ws[2]);
+          if (dist1 && m_ws[2]) {
+            atomicAdd(&g_wide_measure[28], 1ull);
+          }
+        }
+        if (diag) {
+          atomicAdd(&g_wide_measure[20 + (wave & 3)], m_ws[3]);
+        }
+      }
     }
   }
 #endif
@@ -1417,12 +1464,12 @@ hipError_t launch_pair_wide(const PairKernelArgs& a_in, hipStream_t stream, bool
 
 #ifdef LDP_MEASURE
 // (measurement build only) the sums of g_wide_measure since the last reset
-extern "C" int ldp_measure_wide_counters(unsigned long long* out16, int reset) {
-  if (out16 && (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_wide_measure), 16 * sizeof(unsigned long long)) != hipSuccess)) {
+extern "C" int ldp_measure_wide_counters(unsigned long long* out32, int reset) {
+  if (out32 && (hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_wide_measure), 32 * sizeof(unsigned long long)) != hipSuccess)) {
     return 1;
   }
   if (reset) {
-    const unsigned long long zero[16] = {0};
+    const unsigned long long zero[32] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_wide_measure), zero, sizeof(zero)) != hipSuccess) {
       return 1;
     }

@@ -77,7 +77,7 @@ def main():
             wl.step()
             wl.step()
             torch.cuda.synchronize()
-            buf = (ctypes.c_ulonglong * 16)()
+            buf = (ctypes.c_ulonglong * 32)()
             assert L.ldp_measure_wide_counters(buf, 1) == 0
             tag = "%s/%d" % (mode, abl)
             smi.window = tag
@@ -109,6 +109,12 @@ def main():
                 rec["stage_visits_live_dead"] = [m[9], m[10]]
                 if m[11] or m[12] or m[13]:   # the barrier-free kernel: polls at the top of a stage, deferred DMA issues, s_waitcnt vmcnt of the confirmations
                     rec["async_frac_of_wave_cycles"] = {"top_poll_and_issue": m[11] / tot, "deferred_issue_poll": m[12] / tot, "confirm_vmcnt": m[13] / tot}
+            if m[16]:   # the tiles on the diagonal: how many of the workgroup's eight waves their stages ran on, and the live wave-stages of each SIMD (waves s, s + 4)
+                rec["diag_tiles"] = {"tiles": m[16], "stages": m[17], "stages_le4_live_waves": m[18], "stages_one_live_wave": m[19],
+                                     "frac_stages_le4_live_waves": m[18] / m[17] if m[17] else None, "live_wave_stages_per_simd": m[20:24],
+                                     "live_waves_per_stage_mean": sum(m[20:24]) / m[17] if m[17] else None}
+            if m[24]:   # ... and their first neighbours (the corner product of a distance-1 tile keeps one wave, and the CU, to the end of the rows)
+                rec["dist1_tiles"] = {"tiles": m[24], "stages": m[25], "stages_le4_live_waves": m[26], "stages_one_live_wave": m[27], "tiles_with_a_one_wave_stage": m[28]}
             rec.update(smi_summary(tag))
             print(json.dumps(rec), flush=True)
         os.environ.pop("LDP_DEBUG_WIDE_ABLATE", None)
