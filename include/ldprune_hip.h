@@ -134,7 +134,12 @@ typedef struct {
   uint64_t sparse_exact_pairs;     /* few missing calls: pairs the interval test left open and the kernel resolved exactly */
   /* Which matrix-pipe kernel the device-side route gave the pair launches of the last run (one word per launch group, written by
    * route_kernel from the rows' missing-call totals): complete data -> pair_mfma_kernel, a few missing calls -> its interval
-   * epilogue, otherwise the six-product kernel.  All zero when the popcount kernels own the run. */
+   * epilogue, otherwise the six-product kernel.  All zero when the popcount kernels own the run.
+   * The r^2 calls (ldp_r2_unphased_rows / _block / _hits / _block_hits / _band_rows, ldp_pair_stats_block) make ONE launch each and
+   * report it here: route_complete_launches / route_general_launches are 1/0 or 0/1 (the route word of that launch, read from the
+   * records of all resident rows; never the interval epilogue), wide_tiles the tiles attached to that launch (0 when the request took
+   * no tile plan), mfma_block_products the products of its workgroup plan.  All zero on popcount engines ("pair_mfma" 0) and when the
+   * request held no pair. */
   uint32_t route_complete_launches;
   uint32_t route_sparse_launches;
   uint32_t route_general_launches;

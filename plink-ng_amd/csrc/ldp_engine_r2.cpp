@@ -41,7 +41,21 @@ int attach_mfma_plan(ldp_engine* e, PairKernelArgs* A, const std::vector<std::pa
   A->mf_wgs = buf->as<MfmaWG>();
   A->mf_active = 2;
   A->route = e->d_route + slot;
+  // the route word back with the results: route_kernel is queued on this stream already, the callers' synchronise covers the copy
+  HIP_TRY(e, hipMemcpyAsync(reinterpret_cast<uint32_t*>(e->h_counters_pin + 4) + slot, e->d_route + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   return LDP_OK;
+}
+
+// What the r^2 launch just made ran on (include/ldprune_hip.h, ldp_counters): the route word of its slot, its tiles and its planned
+// products.  Call after the stream that carried the launch has been synchronised.  Popcount engines report zeros.
+void report_r2_plan(ldp_engine* e, const PairKernelArgs& A, bool on_mfma, uint64_t products) {
+  const bool routed = on_mfma && A.n_mf_wgs;
+  const uint32_t route = routed ? reinterpret_cast<const uint32_t*>(e->h_counters_pin + 4)[e->groups.size()] : 0;
+  e->ctr.route_complete_launches = (routed && (route == 0)) ? 1 : 0;
+  e->ctr.route_general_launches = (routed && (route != 0)) ? 1 : 0;  // (never the interval epilogue: every r^2 is wanted)
+  e->ctr.route_sparse_launches = 0;
+  e->ctr.wide_tiles = routed ? A.n_wd_tiles : 0;
+  e->ctr.mfma_block_products = routed ? products : 0;
 }
 
 struct HitRequest {
@@ -185,6 +199,7 @@ int r2_band_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_floa
     HIP_TRY(e, hipEventElapsedTime(&kms_fast, evk[0], evk[1]));
     HIP_TRY(e, hipEventElapsedTime(&kms_general, evk[2], evk[3]));
   }
+  report_r2_plan(e, A, on_mfma, mf_products);
   e->ctr.candidate_pairs = n_elems;
   e->ctr.ms_pair_fast = kms_fast;
   e->ctr.ms_pair_general = kms_general;
@@ -391,6 +406,7 @@ int r2_rows_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_floa
       memcpy(static_cast<double*>(out) + idx, &bits, 8);
     }
   }
+  report_r2_plan(e, A, on_mfma, mf_products);
   e->ctr.candidate_pairs = cand;
   e->ctr.computed_pairs = computed;
   e->ctr.ms_pair_fast = kms_fast;

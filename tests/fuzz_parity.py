@@ -5,7 +5,9 @@ both scan orders, thresholds from 0.02 to 0.95, missing rates from 0 to 20 %, LD
 rows, several chromosomes.  Compared per case: the prune set with the oracle's, and the decision of EVERY candidate pair (the predicate
 rows of the production run, LdPruneEngine.last_pred) with the float64 reference of ldtools (band_pair_stats / band_decisions).  Prints
 the first mismatching case (seed) and exits non-zero.
-    python tests/fuzz_parity.py [--cases 150] [--seed 1] [--mixed | --wide-missing | --wide-sparse | --wide-async]"""
+    python tests/fuzz_parity.py [--cases 150] [--seed 1] [--mixed | --wide-missing | --wide-sparse | --wide-async | --r2]
+--r2: the r^2 outputs of complete-data launches instead (rows, a column block and the hit filter of random all-pairs requests, every value
+bit for bit against ldtools.band_r2; the counters must show the complete route)."""
 import argparse
 import os
 import sys
@@ -116,6 +118,78 @@ def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=Fa
     return ok, desc
 
 
+def r2_case(pkg, rng, idx):
+    """--r2: complete data, m from 385 (where tiles begin) to 1,500, n from 2 to 3,000, wide_min_reach in {0, 12, 1e9}: a random row chunk
+    (doubles or floats), a random column block and the hits of a random chunk at a random threshold, r^2 or signed r"""
+    m = int(rng.integers(385, 1501))
+    n = int(rng.choice([2, 3, 31, 64, 90, 511, 512, 513, 1024, 1025, int(rng.integers(2, 3001)), int(rng.integers(2, 3001))]))
+    raw = T.synth_raw_codes(m, n, seed=int(rng.integers(1, 1 << 30)), missing_rate=0.0, ld_copy_prob=0.6, redraw=0.1)
+    for _ in range(m // 6):
+        a = int(rng.integers(1, m))
+        src = int(rng.integers(0, a))
+        row = np.where(rng.random(n) < rng.choice([0.5, 0.8, 0.95, 1.0]), raw[src], raw[a])
+        raw[a] = 2 - row if rng.random() < 0.3 else row
+    for v in rng.integers(0, m, size=3):
+        raw[int(v)] = int(rng.integers(0, 3))
+    reach = float(rng.choice([0, 12, 1e9]))
+    mode = int(rng.choice([0, 0, 1, 2]))
+    lo = np.zeros(m, dtype=np.int64)
+    first, second = T.band_pairs(lo)
+    band = T.band_r2(T.band_pair_stats(raw, lo, orient=(mode != 2)), signed=1 if mode else 0)
+    full = T.band_to_dense(band, lo, 0, m, 0, m, diag=T.self_r2(raw))
+    eng = pkg.LdPruneEngine(n, 2, 1, False, 0.5, device=0)
+    eng.set_option("wide_min_reach", reach)
+    if idx % 4 == 3:
+        eng.set_option("orient_rows", 0)
+    eng.set_variants_matrix(m)
+    eng.load_genotypes_host(0, T.pack_2bit(raw), pkg.LDP_GENO_REF)
+    eng.set_r_signed(mode)
+    wrong, tiles = [], 0
+
+    def route(what, has_pairs):
+        c = eng.counters()
+        if has_pairs and (c["route_complete_launches"], c["route_general_launches"]) != (1, 0):   # (a request without a pair may plan nothing)
+            wrong.append("%s: not on the complete route %s" % (what, c))
+        return c["wide_tiles"]
+
+    r0 = int(rng.integers(0, m))
+    rc = int(rng.integers(1, m - r0 + 1))
+    as_float = bool(rng.random() < 0.5)
+    got = eng.r2_unphased_rows(r0, rc, as_float=as_float)
+    tiles += route("rows", r0 + rc > 1)
+    want = full[r0:r0 + rc, :r0 + rc]
+    want = T.r2_to_float32(want) if as_float else want
+    bad = np.argwhere(T.bits_of(got) != T.bits_of(want))
+    if len(bad):
+        wrong.append("rows(%d, %d, float=%s): %d differ, first (i=%d, j=%d) got %r want %r" % (r0, rc, as_float, len(bad), bad[0][1], r0 + bad[0][0], got[tuple(bad[0])], want[tuple(bad[0])]))
+    b0 = int(rng.integers(0, m))
+    bc = int(rng.integers(1, m - b0 + 1))
+    c0 = int(rng.integers(0, m))
+    cc = int(rng.integers(1, m - c0 + 1))
+    got = eng.r2_unphased_block(b0, bc, c0, cc, as_float=not as_float)
+    tiles += route("block", c0 < b0 + bc - 1)
+    want = full[b0:b0 + bc, c0:c0 + cc]
+    want = want if as_float else T.r2_to_float32(want)
+    bad = np.argwhere(T.bits_of(got) != T.bits_of(want))
+    if len(bad):
+        wrong.append("block(%d, %d, %d, %d): %d differ, first (i=%d, j=%d) got %r want %r" % (b0, bc, c0, cc, len(bad), c0 + bad[0][1], b0 + bad[0][0], got[tuple(bad[0])], want[tuple(bad[0])]))
+    thr = float(rng.choice([0.0, 1e-9, 0.05, 0.2, 0.5]))
+    hits, found = eng.r2_unphased_block_hits(thr, b0, bc, c0, cc, capacity=m * m // 2 + 1)
+    tiles += route("hits", c0 < b0 + bc - 1)
+    with np.errstate(invalid="ignore"):
+        sel = (second >= b0) & (second < b0 + bc) & (first >= c0) & (first < c0 + cc) & (np.abs(band) >= thr)
+    order = np.lexsort((second[sel], first[sel]))
+    f, s, v = first[sel][order], second[sel][order], band[sel][order]
+    if not (found == len(f) == len(hits) and np.array_equal(hits["first"].astype(np.int64), f) and np.array_equal(hits["second"].astype(np.int64), s)
+            and np.array_equal(T.bits_of(hits["r2"]), T.bits_of(v))):
+        wrong.append("block_hits(%g, %d, %d, %d, %d): found %d, returned %d, reference %d (or values differ)" % (thr, b0, bc, c0, cc, found, len(hits), len(f)))
+    eng.close()
+    desc = "case %d: n=%d m=%d wide_min_reach=%g signed=%d rows=(%d, %d) block=(%d, %d, %d, %d) thr=%g tiles=%d hits=%d" % (idx, n, m, reach, mode, r0, rc, b0, bc, c0, cc, thr, tiles, len(f))
+    if wrong:
+        desc += "\n" + "\n".join(wrong)
+    return not wrong, desc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=150)
@@ -124,10 +198,21 @@ def main():
     ap.add_argument("--wide-sparse", action="store_true", help="every case has a FEW missing calls (0.01-0.5 %%) and takes the tile plan: pair_mfma_wide_kernel's SPARSE instantiation")
     ap.add_argument("--wide-async", action="store_true", help="every case is complete data on the tile plan, run by pair_mfma_wide_async_kernel (engine option wide_async)")
     ap.add_argument("--mixed", action="store_true", help="the rows' missing rate is drawn per block of rows from {0, 0.1 %%, 5 %%}: mixed-missingness filesets")
+    ap.add_argument("--r2", action="store_true", help="the r^2 outputs of complete-data launches (rows, blocks, hits) against ldtools.band_r2")
     args = ap.parse_args()
     pkg = ge.load_package()
     rng = np.random.default_rng(args.seed)
     t0 = time.time()
+    if args.r2:
+        for k in range(args.cases):
+            ok, desc = r2_case(pkg, rng, k)
+            if not ok:
+                print("MISMATCH", desc, "(--r2 --seed %d)" % args.seed)
+                sys.exit(1)
+            if k % 25 == 0:
+                print(desc, flush=True)
+        print("%d r^2 cases bit-identical to the reference, %.1f s" % (args.cases, time.time() - t0))
+        return
     skipped_any = sparse_tiles = 0
     for k in range(args.cases):
         ok, desc = one_case(pkg, rng, k, args.wide_missing, args.wide_async, args.wide_sparse, args.mixed)

@@ -744,13 +744,15 @@ def band_pairs(lo):
     return first, second
 
 
-def band_pair_stats(raw, lo, block=256):
+def band_pair_stats(raw, lo, block=256, orient=True):
     """The six integers (nm, sum1, ssq1, sum2, ssq2, dot) of EVERY candidate pair (i, j), lo[j] <= i < j, as a (pairs, 6) int64
     array in band order (band_pairs).  raw: REF-based codes (M, N); every variant is oriented on its major allele (REF unless
     ref_ct * (1 / total) < 0.5, the definition of plink2_common.h:559-567; an exact tie goes to REF), x = +1 hom-major, 0 het,
     -1 hom-minor, and the sums run over the samples both variants have a call for.  Plain float64 matrix products of the
     three indicator / valued matrices (call present, homozygous, x): every sum is an integer far below 2^53, so the products
-    are exact whatever order BLAS adds in.  Shares no code with oracle/ldoracle.c or with the kernels."""
+    are exact whatever order BLAS adds in.  Shares no code with oracle/ldoracle.c or with the kernels.
+    orient=False: every row keeps the REF orientation (x = +1 hom-REF, -1 hom-ALT; the statistics behind the REF-oriented r of
+    --r-unphased, ldp_set_r_signed(2)) -- no major allele is looked at, nothing is flipped afterwards."""
     raw = np.asarray(raw)
     lo = np.asarray(lo, dtype=np.int64)
     m, n = raw.shape
@@ -760,7 +762,7 @@ def band_pair_stats(raw, lo, block=256):
     ref_ct = 2 * n_ref + n_het
     tot = ref_ct + 2 * n_alt + n_het
     ref_freq = np.where(tot > 0, ref_ct.astype(np.float64) * (1.0 / np.maximum(tot, 1).astype(np.float64)), 0.5)
-    sign = np.where(ref_freq >= 0.5, 1.0, -1.0)
+    sign = np.where(ref_freq >= 0.5, 1.0, -1.0) if orient else np.ones(m)
     C = (raw != 3).astype(np.float64)
     H = ((raw == 0) | (raw == 2)).astype(np.float64)
     X = ((raw == 0).astype(np.float64) - (raw == 2).astype(np.float64)) * sign[:, None]
@@ -794,6 +796,73 @@ def band_cov_vars(stats):
     """(cov12, var1, var2) as float64 arrays: the integer parts in int64 (plink2_ld.cc:1085-1087), then one conversion each."""
     nm, s1, q1, s2, q2, dot = _stats_columns(stats)
     return (dot * nm - s1 * s2).astype(np.float64), (q1 * nm - s1 * s1).astype(np.float64), (q2 * nm - s2 * s2).astype(np.float64)
+
+
+R2_NAN64 = 0xfff8000000000000   # what the reference's 0.0 / 0.0 leaves on x86; its float32 cast is R2_NAN32
+R2_NAN32 = 0xffc00000
+
+
+def band_r2(stats, signed=0):
+    """r^2 of every pair as ComputeR2 forms it (plink2_ld.cc:6654-6682), float64, from the six integers: both variances and the
+    covariance in int64 with ONE conversion each, variance_prod = var0 * var1, NaN (R2_NAN64) when nm == 0 or variance_prod == 0.0,
+    otherwise (cov * cov) / variance_prod -- separate numpy operations, each rounded on its own, nothing fused.
+    signed=1: r = +-sqrt(r^2) with the sign of the int64 covariance (--r-unphased); a zero covariance gives +0.0, NaN stays NaN.
+    The orientation is the statistics': band_pair_stats(..., orient=False) gives the REF-oriented r."""
+    nm, s1, q1, s2, q2, dot = _stats_columns(stats)
+    var0 = (q1 * nm - s1 * s1).astype(np.float64)
+    var1 = (q2 * nm - s2 * s2).astype(np.float64)
+    cov_int = dot * nm - s1 * s2
+    cov = cov_int.astype(np.float64)
+    variance_prod = var0 * var1
+    undefined = (nm == 0) | (variance_prod == 0.0)
+    num = cov * cov
+    out = num / np.where(undefined, 1.0, variance_prod)
+    if signed:
+        out = np.sqrt(out)
+        neg = cov_int < 0
+        out[neg] = -out[neg]
+    out.view(np.uint64)[undefined] = R2_NAN64
+    return out
+
+
+def r2_to_float32(values):
+    """the float32 form of the r^2 outputs: the IEEE cast of the double, NaN as R2_NAN32"""
+    values = np.asarray(values, dtype=np.float64)
+    nan = np.isnan(values)
+    out = np.where(nan, 0.0, values).astype(np.float32)
+    out.view(np.uint32)[nan] = R2_NAN32
+    return out
+
+
+def self_r2(raw):
+    """the diagonal of the r^2 matrix: r^2(v, v) through the same formula = 1.0, or NaN for a variant without variance"""
+    raw = np.asarray(raw)
+    nm = (raw != 3).sum(1).astype(np.int64)
+    s = (raw == 0).sum(1).astype(np.int64) - (raw == 2).sum(1).astype(np.int64)
+    q = ((raw == 0) | (raw == 2)).sum(1).astype(np.int64)
+    st = np.stack([nm, s, q, s, q, q], 1)
+    return band_r2(st)
+
+
+def band_to_dense(values, lo, row_first, row_ct, col_first, col_ct, diag=None):
+    """Band-order values (band_pairs(lo) order; (pairs,) or (pairs, k)) scattered into the dense layout the engine returns for rows
+    [row_first, +row_ct) x columns [col_first, +col_ct): element [j - row_first, i - col_first] for the pairs i < j of the band inside
+    the block, `diag[j]` at i == j where given, zero bits everywhere else."""
+    values = np.asarray(values)
+    first, second = band_pairs(lo)
+    out = np.zeros((row_ct, col_ct) + values.shape[1:], dtype=values.dtype)
+    sel = (second >= row_first) & (second < row_first + row_ct) & (first >= col_first) & (first < col_first + col_ct)
+    out[second[sel] - row_first, first[sel] - col_first] = values[sel]
+    if diag is not None:
+        j = np.arange(max(row_first, col_first), min(row_first + row_ct, col_first + col_ct), dtype=np.int64)
+        out[j - row_first, j - col_first] = np.asarray(diag)[j]
+    return out
+
+
+def bits_of(a):
+    """the bit patterns of a float32 / float64 array (comparisons of r^2 outputs are on these: NaN payloads and signed zeros count)"""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
 
 
 def band_decisions(stats, r2):

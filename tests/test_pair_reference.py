@@ -76,6 +76,71 @@ def test_every_pair_of_a_band_equals_the_oracle(pkg, n, is_bp, window):
     print("pairs compared: %d x 4 thresholds" % cand)
 
 
+@pytest.mark.parametrize("n", [2, 63, 64, 65, 1025])
+def test_every_r2_of_all_pairs_equals_the_oracle(n):
+    """ldtools.band_r2 / r2_to_float32 / the REF-oriented r (what tests/test_r2_complete.py compares the r^2 outputs with), all pairs of
+    the edge rows: bit for bit the oracle's integers through ComputeR2's operations, the IEEE float32 cast, and the REF orientation --
+    obtained from REF-oriented products -- against sign(cov) x (one of the two variants is ALT-major) from the oracle's major alleles."""
+    m = 64
+    raw = edge_rows(m, n, seed=100 + n)
+    lo = np.zeros(m, dtype=np.int64)
+    first, second = T.band_pairs(lo)
+    assert len(first) == m * (m - 1) // 2
+    stats = T.band_pair_stats(raw, lo)
+    r2 = T.band_r2(stats)
+    r_major = T.band_r2(stats, signed=1)
+    r_ref = T.band_r2(T.band_pair_stats(raw, lo, orient=False), signed=1)
+    inv, mf, altmaj = T.oracle_prepare(raw)
+    hom, r2h, vaggs = T.oracle_split(inv, n)
+    want = np.zeros(len(first), dtype=np.float64)
+    want_major = np.zeros(len(first), dtype=np.float64)
+    want_ref = np.zeros(len(first), dtype=np.float64)
+    nan = np.array([T.R2_NAN64], dtype=np.uint64).view(np.float64)[0]
+    for k in range(len(first)):
+        i, j = int(first[k]), int(second[k])
+        st = T.oracle_pair_stats(hom, r2h, vaggs, n, i, j)
+        cov, v1, v2 = T.oracle_r2(st)
+        prod = v1 * v2
+        if st.nm == 0 or prod == 0.0:
+            want[k] = want_major[k] = want_ref[k] = nan
+            continue
+        want[k] = cov * cov / prod
+        r = float(np.sqrt(np.float64(want[k])))
+        sign = (cov > 0) - (cov < 0)
+        want_major[k] = -r if sign < 0 else r
+        sign_ref = sign * (-1 if (altmaj[i] ^ altmaj[j]) else 1)
+        want_ref[k] = -r if sign_ref < 0 else r
+    assert np.array_equal(T.bits_of(r2), T.bits_of(want)), np.flatnonzero(T.bits_of(r2) != T.bits_of(want))[:5]
+    assert np.array_equal(T.bits_of(r_major), T.bits_of(want_major))
+    assert np.array_equal(T.bits_of(r_ref), T.bits_of(want_ref)), np.flatnonzero(T.bits_of(r_ref) != T.bits_of(want_ref))[:5]
+    isn = np.isnan(want)
+    assert isn.sum() >= 4 * (m - 1) - 6 and (T.bits_of(r2)[isn] == T.R2_NAN64).all()     # the four monomorphic rows against everything
+    for vals in (r2, r_major, r_ref):
+        f32 = T.r2_to_float32(vals)
+        assert f32.dtype == np.float32
+        assert (T.bits_of(f32)[isn] == T.R2_NAN32).all()
+        assert np.array_equal(T.bits_of(f32)[~isn], T.bits_of(np.float32(vals[~isn])))
+    # +0.0 at a zero covariance in either orientation; both signs and both orientations occur
+    zero = ~isn & (want == 0.0)
+    assert not T.bits_of(r_major)[zero].any() and not T.bits_of(r_ref)[zero].any()
+    if n > 2:
+        assert (want_major[~isn] < 0).any() and (want_major[~isn] > 0).any() and (np.signbit(r_ref) != np.signbit(r_major)).any()
+    # the diagonal and the dense layout
+    d = T.self_r2(raw)
+    for v in range(m):
+        st = T.oracle_pair_stats(hom, r2h, vaggs, n, v, v)
+        cov, v1, v2 = T.oracle_r2(st)
+        w = nan if (st.nm == 0 or v1 * v2 == 0.0) else cov * cov / (v1 * v2)
+        assert T.bits_of(np.float64(d[v]))[()] == T.bits_of(np.float64(w))[()], v
+    dense = T.band_to_dense(r2, lo, 10, 30, 5, 20, diag=d)
+    for j in range(10, 40):
+        for i in range(5, 25):
+            k = j * (j - 1) // 2 + i
+            w = r2[k] if i < j else (d[j] if i == j else 0.0)
+            assert T.bits_of(np.float64(dense[j - 10, i - 5]))[()] == T.bits_of(np.float64(w))[()], (i, j)
+    print("pairs compared: %d (r^2, r major-oriented, r REF-oriented, float32 casts)" % len(first))
+
+
 def test_decisions_from_a_structured_stats_array(pkg):
     """band_decisions takes the device's own tuples (ldp_pair_stats_t) as well"""
     raw = edge_rows(40, 130, seed=5)

@@ -47,6 +47,9 @@ def test_matrix_rows_match_oracle(gpu_pkg, m, n, miss):
     eng.set_variants_matrix(m)
     eng.load_genotypes_host(0, T.pack_2bit(raw), pkg.LDP_GENO_REF)
     got = eng.r2_unphased_rows()
+    # (the all-missing row 5 routes EVERY case here, miss = 0.0 included, to the six-product kernel: the route reads the records of all
+    # resident rows.  tests/test_r2_complete.py has the complete-data kernels.)
+    assert eng.counters()["route_general_launches"] == 1 and eng.counters()["route_complete_launches"] == 0
     il = np.tril_indices(m)
     nan_w, nan_g = np.isnan(want[il]), np.isnan(got[il])
     assert np.array_equal(nan_w, nan_g)
@@ -359,6 +362,8 @@ def test_pair_tuples_of_dense_blocks_from_the_pair_kernels(gpu_pkg, m, n, miss, 
     eng.load_genotypes_host(0, T.pack_2bit(raw), pkg.LDP_GENO_REF)
     for (r0, rc, c0, cc) in [(0, m, 0, m), (100, 45, 37, 50), (64, 64, 64, 64), (130, m - 130, 96, 54)]:
         blk = eng.pair_stats_block(r0, rc, c0, cc)
+        # (row 5 misses every call: also the miss = 0.0 case runs the six-product kernel; popcount engines report no route)
+        assert eng.counters()["route_general_launches"] == mfma and eng.counters()["route_complete_launches"] == 0
         first, second = [], []
         for j in range(r0, r0 + rc):
             for i in range(c0, min(j, c0 + cc)):
