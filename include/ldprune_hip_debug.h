@@ -54,9 +54,14 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
  *                     SPARSE instantiation; default 1); 0 = they fall back to the parallelogram plan as in rounds 2-5
  *   "wide_diag_kernel" 0/1: complete-data prune launches run the tiles ON the diagonal (36 live products, to the end of the rows) in eight 2 x 3
  *                     rectangles, a second body of pair_mfma_wide_kernel picked per workgroup (default 1); 0 = 2 x 4 rectangles for every tile
+ *   "wide_diag_corner" 0/1: where "wide_diag_kernel" applies, the diagonal tile also computes the one product of its J tile's distance-1 tile that
+ *                     lies next to the block diagonal -- (J block 0, V block 7), row-block 8 t against 8 t - 1 -- in a slot of its wave 0 that is
+ *                     otherwise beyond the plan, and the distance-1 tile retires with the far tiles (default 1); 0 = every tile computes its own
+ *                     products.  The plan (ldp_debug_wide_plan) is the same either way
  *   "wide_diag_last"  k: within a launch every XCD's stream of 8 x 8 tiles runs its far tiles first and the tiles fewer than k tile
- *                     distances from the diagonal (the long ones: they hold the pairs in LD) at the end; 0 = plain J order (default 2;
- *                     before ldp_set_variants())
+ *                     distances from the diagonal (the long ones: they hold the pairs in LD) at the end; 0 = plain J order (default 1: the
+ *                     diagonal tiles, which with "wide_diag_corner" hold every product next to the block diagonal; 2 until then; before
+ *                     ldp_set_variants())
  *   "wide_min_reach"  row-blocks a subcontig's band must reach to take the 8 x 8 tile plan of the wide-band kernel; 0 = always,
  *                     a huge value = never (before ldp_set_variants())
  *   "replay_steps"    k: ldp_debug_replay_pairs() walks every subcontig in k instalments, the way the streaming replay of a run advances

@@ -203,11 +203,30 @@ constexpr bool wd_diag_near_on_four_waves() {
 }
 static_assert(wd_diag_partitions(), "the eight owned sets partition the 36 products with v <= j exactly");
 static_assert(wd_diag_near_on_four_waves(), "waves 0-3 own every (j, j) and (j, j - 1)");
+// The CORNER product (PairKernelArgs::wd_diag_corner).  The tile one tile distance from the diagonal, (J tile t, V tile t - 1), holds exactly one product
+// next to the block diagonal: (J block 0, V block 7), row-block 8 t against 8 t - 1.  It outlives the checkpoints wherever neighbouring variants are in
+// LD, and its wave -- one wave of a workgroup that keeps a CU -- then runs its whole rectangle to the end of the rows.  Wave kWdDiagCornerWave of the
+// DIAGONAL tile's map multiplies J block 0 with a column (kWdDiagCornerCol) that holds no product of the triangle: both slots are beyond the plan,
+// computed at every stage and never live.  On a launch with wd_diag_corner that column reads row-block slot kWdTile, defined for a diagonal tile as the
+// 32 rows in front of it (a ninth staged row-block, while the product lives), and its J-block-a0 slot IS the corner product; the distance-1 tile drops
+// bit (0, 7) of its mask.  kWdDiagMap and what ldp_debug_wide_diag_map() exports are the map of the TRIANGLE and do not change.
+constexpr uint32_t kWdDiagCornerWave = 0;
+constexpr uint32_t kWdDiagCornerCol = 2;
+constexpr bool wd_diag_corner_free() {
+  const WdDiagRect& r = kWdDiagMap[kWdDiagCornerWave];
+  // J block 0 is the wave's first; the column lies above the diagonal for both J blocks of the rectangle: no owned product, and no J block's slot
+  return (kWdDiagCornerWave < 4) && (r.a0 == 0) && (kWdDiagCornerCol < static_cast<uint32_t>(kWdDiagCols)) && (r.b0 + kWdDiagCornerCol > r.a0 + 1u) &&
+         !(wd_diag_owned(kWdDiagCornerWave) & ((1ull << (8 * r.a0 + r.b0 + kWdDiagCornerCol)) | (1ull << (8 * (r.a0 + 1) + r.b0 + kWdDiagCornerCol))));
+}
+static_assert(wd_diag_corner_free(), "the corner column owns no product of the triangle in its wave's rectangle, and the wave is one of the near waves 0-3");
+// MfmaTile::pad of the tiles of a LAUNCH array (the plan's tiles carry 0): the corner product of this J tile is in the plan, and ...
+constexpr uint32_t kWdPadCornerTaken = 1;  // ... this diagonal tile computes it on a launch with wd_diag_corner
+constexpr uint32_t kWdPadCornerGiven = 2;  // ... this distance-1 tile leaves it to the diagonal tile on such a launch
 struct MfmaTile {
   int32_t jv;        // first variant of J block 0 (J block a = jv + 32 a)
   int32_t vv;        // first variant of V block 0 (V block b = vv + 32 b); == jv on the diagonal
   uint32_t jend;     // second variants >= jend belong to the next subcontig
-  uint32_t pad;
+  uint32_t pad;      // launch arrays: kWdPadCorner* (above); the plan's tiles: 0
   uint64_t mask;     // bit 8 a + b: product (J_a, V_b) holds candidate pairs
 };
 
@@ -280,6 +299,8 @@ struct PairKernelArgs {
                                  // pair_mfma_kernel<., SPARSE = true> then skips the workgroups of their subcontigs as the complete-data kernel does
   uint32_t wd_diag_split;        // complete-data prune launches: the tiles on the diagonal take the kernel's 2 x 3 body (kWdDiagMap: 2 x 3 rectangles on all eight
                                  // waves), picked per workgroup (EngineOptions::wide_diag_kernel)
+  uint32_t wd_diag_corner;       // ... and take the corner product of the distance-1 tile of their J tile (kWdDiagCornerWave; EngineOptions::wide_diag_corner);
+                                 // only with wd_diag_split
 };
 
 constexpr uint32_t kRouteComplete = 0, kRouteSparse = 1, kRouteGeneral = 2;

@@ -318,7 +318,7 @@ EngineOptions options_from_env() {
   const char* ws = LDP_ENV("LDP_WIDE_SPARSE");
   o.wide_sparse = !(ws && (strcmp(ws, "0") == 0));
   const char* dl = LDP_ENV("LDP_DEBUG_WIDE_DIAG_LAST");
-  o.wide_diag_last = dl ? static_cast<uint32_t>(std::max(0, atoi(dl))) : 2u;
+  o.wide_diag_last = dl ? static_cast<uint32_t>(std::max(0, atoi(dl))) : 1u;
   if (const char* wa = LDP_ENV("LDP_DEBUG_WIDE_ASYNC")) {
     o.wide_async = (atoi(wa) != 0);
   }
@@ -827,6 +827,8 @@ void build_shard(ldp_engine* e) {
     // by J tile, and the tiles next to the diagonal at the end -- the diagonal ones and their first neighbours, which hold the rest
     // of the pairs in LD (config 3's share, kernel ms with the last 0 / 1 / 2 / 3 / 4 tile distances deferred: 330 / 302 / 296 / 297 /
     // 319; HBM traffic 6.1 -> 5.3 x compulsory with 1).  Streams are padded to equal length with empty tiles (mask 0).
+    // Since the diagonal tile computes the corner product of its J tile's distance-1 tile (below), that neighbour retires with the far tiles on the bench's
+    // generator and runs among them: wide_diag_last = 1 (the bench line's pair kernels 254.7 -> 247.2 ms against 2, profiles/diag_corner.md).
     // the diagonal tiles' own body owns the 36 products on and below the diagonal (kWdDiagMap, ldp_device.h): every prune plan's diagonal tile lies
     // inside; a plan that does not keeps the 2 x 4 body for them
     uint64_t diag_owned = 0;
@@ -851,6 +853,22 @@ void build_shard(ldp_engine* e) {
         const uint32_t dist = static_cast<uint32_t>(e->wd_tiles[t].jv - e->wd_tiles[t].vv) / (kMfBlock * kWdTile);
         ((dist < e->opt.wide_diag_last) ? diag : off).push_back(t);
       }
+      // The corner product (ldp_device.h: kWdDiagCornerWave): where the plan holds (J block 0, V block 7) of a distance-1 tile AND the diagonal tile of the same
+      // J tile (its neighbour in the plan's order, same launch), the launch array says so on both -- the plan itself (wd_tiles, debug_wide_plan) describes every
+      // product in the tile that covers it, whatever the launch does.
+      std::vector<uint32_t> corner_pad(g.wd_ct, 0);
+      for (uint32_t t = g.wd_first; t + 1 < g.wd_first + g.wd_ct; ++t) {
+        const MfmaTile &d1 = e->wd_tiles[t], &dg = e->wd_tiles[t + 1];
+        if ((dg.jv == dg.vv) && (d1.jv == dg.jv) && (d1.jv - d1.vv == static_cast<int32_t>(kMfBlock * kWdTile)) && ((d1.mask >> (kWdTile - 1)) & 1u)) {
+          corner_pad[t - g.wd_first] = kWdPadCornerGiven;
+          corner_pad[t + 1 - g.wd_first] = kWdPadCornerTaken;
+        }
+      }
+      auto launch_tile = [&](uint32_t t) {
+        MfmaTile tl = e->wd_tiles[t];
+        tl.pad = corner_pad[t - g.wd_first];
+        return tl;
+      };
       auto chunk = [](size_t n, uint32_t x) { return std::make_pair(n * x / 8, n * (x + 1) / 8); };
       size_t per = 0;
       for (uint32_t x = 0; x < 8; ++x) {
@@ -863,10 +881,10 @@ void build_shard(ldp_engine* e) {
         const auto co = chunk(off.size(), x), cd = chunk(diag.size(), x);
         size_t k = 0;
         for (size_t q = co.first; q < co.second; ++q, ++k) {
-          e->wd_launch.push_back(e->wd_tiles[off[q]]);
+          e->wd_launch.push_back(launch_tile(off[q]));
         }
         for (size_t q = cd.first; q < cd.second; ++q, ++k) {
-          e->wd_launch.push_back(e->wd_tiles[diag[q]]);
+          e->wd_launch.push_back(launch_tile(diag[q]));
         }
         for (; k < per; ++k) {
           e->wd_launch.push_back(empty);
@@ -1614,6 +1632,8 @@ int ldp_debug_set_option(ldp_engine* e, const char* name, double value) {
     e->opt.csr_capacity = static_cast<uint64_t>(std::max(0.0, value));
   } else if (n == "wide_diag_kernel") {
     e->opt.wide_diag_kernel = (value != 0.0);
+  } else if (n == "wide_diag_corner") {
+    e->opt.wide_diag_corner = (value != 0.0);
   } else if (n == "wide_sparse") {
     e->opt.wide_sparse = (value != 0.0);
   } else if (n == "replay_steps") {

@@ -188,12 +188,15 @@ struct EngineOptions {
   bool pair_four = true;      // LDP_PAIR_FOUR=0: rows with missing calls always take all six products (prune launches otherwise four)
   bool pair_gu = true;        // option "pair_gu" 0: the four-product form multiplies x and n (rounds 2-3) instead of allele counts and missing flags
   bool four_tiles = true;     // LDP_PAIR_FOUR_TILES=0: the four-product form stays on the parallelogram plan in wide bands too
-  uint32_t wide_diag_last = 2; // LDP_DEBUG_WIDE_DIAG_LAST=k: tiles fewer than k tile distances from the diagonal run at the end of their XCD stream (0: plain J order)
+  uint32_t wide_diag_last = 1; // LDP_DEBUG_WIDE_DIAG_LAST=k: tiles fewer than k tile distances from the diagonal run at the end of their XCD stream (0: plain J order).
+                               // 1 since the diagonal tiles take the corner product (wide_diag_corner): the distance-1 tiles no longer run long
   uint64_t csr_capacity = 0;   // test hook "csr_capacity" k: the CSR buffer holds k entries (0: a quarter of the predicate words), to force the dense fallback
   bool orient_rows = true;     // option "orient_rows" 0: ALT-major rows stay in the image as the input had them (rounds 2-5); default: the count pass stores them
                                // inverted, so that every row of the image is major-allele-oriented (ldp_device.h)
   bool pred_csr = true;        // option "pred_csr" 0: prune runs copy their dense predicate rows back (rounds 1-5) instead of the non-zero words (ldp_pred_csr.hip)
   bool wide_diag_kernel = true;  // option "wide_diag_kernel" 0: diagonal tiles stay with the 2 x 4 kernel (rounds 2-5)
+  bool wide_diag_corner = true;  // option "wide_diag_corner" 0: the distance-1 tile keeps its corner product (J block 0, V block 7); 1: the diagonal tile of the same J tile
+                                 // computes it (ldp_device.h: kWdDiagCornerWave).  Honoured where wide_diag_kernel is
   bool wide_sparse = true;     // LDP_WIDE_SPARSE=0 / option "wide_sparse" 0: launches with a few missing calls leave the 8 x 8 tiles for the parallelogram plan (rounds 2-5)
   bool wide_async = false;     // option "wide_async": the 8 x 8 tiles on pair_mfma_wide_async_kernel (flags instead of a workgroup barrier per stage)
   // test hooks (ldp_debug_set_option only; 0 = off): results never depend on them

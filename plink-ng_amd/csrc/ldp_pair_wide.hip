@@ -371,10 +371,23 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
   const int32_t jv0 = __builtin_amdgcn_readfirstlane(tile->jv);
   const int32_t vv0 = __builtin_amdgcn_readfirstlane(tile->vv);
   const uint32_t jend = __builtin_amdgcn_readfirstlane(tile->jend);
-  const uint32_t mask_lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tile->mask));
+  uint32_t mask_lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tile->mask));
   const uint32_t mask_hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tile->mask >> 32));
+  // The CORNER product (PairKernelArgs::wd_diag_corner, ldp_device.h): (J block 0, V block 7) of the tile one tile distance from the diagonal --
+  // row-block 8 t against 8 t - 1, next to the block diagonal, so it outlives the checkpoints like the near products -- is computed by the DIAGONAL
+  // tile of the same J tile, in a slot of its corner wave that is otherwise beyond the plan.  The distance-1 tile drops it here and retires with
+  // the far tiles; `corner`: this (diagonal) tile has taken it.
+  bool corner = false;
+  if constexpr ((ABL == 0) && !SPARSE) {
+    const uint32_t pad = __builtin_amdgcn_readfirstlane(tile->pad);
+    if constexpr (VC == 3) {
+      corner = A.wd_diag_corner && ((pad & kWdPadCornerTaken) != 0);
+    } else if (A.wd_diag_corner && (pad & kWdPadCornerGiven)) {
+      mask_lo &= ~(1u << (kWdTile - 1));
+    }
+  }
   if (!(mask_lo | mask_hi)) {
-    return;  // (padding of an XCD's stream: the launch's streams are of equal length, ldp_engine.cpp build_shard)
+    return;  // (padding of an XCD's stream: the launch's streams are of equal length, ldp_engine.cpp build_shard; or a distance-1 tile that held the corner only)
   }
   const bool diag = (jv0 == vv0);
   [[maybe_unused]] const int32_t g_bias = g_bias_of(A.founder_ct, kWdStageSamples);
@@ -401,7 +414,24 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
   const uint32_t vslot0 = (diag ? 0u : static_cast<uint32_t>(kWdTile)) + b0;
   auto mask_row = [&](uint32_t a) { return ((a < 4) ? (mask_lo >> (8 * a)) : (mask_hi >> (8 * (a - 4)))) & 0xffu; };
   uint32_t live = ((mask_row(a0) >> b0) & own) | (((mask_row(a0 + 1) >> b0) & own) << VC);
+  // the corner wave's corner column reads row-block slot kWdTile -- the 32 rows in front of the tile -- instead of V block b0 + kWdDiagCornerCol, and its
+  // J-block-a0 product there is the corner product: live from the start.  The column's other product (J block a0 + 1) stays unowned.
+  const bool corner_wave = corner && (wave == kWdDiagCornerWave);
+  const uint32_t corner_col = corner_wave ? kWdDiagCornerCol : 0xffu;  // (uniform; no column of any other wave)
+  if (corner_wave) {
+    live |= 1u << kWdDiagCornerCol;
+  }
   live = __builtin_amdgcn_readfirstlane(live);
+  // row-block slots wave w reads while the products `l` of its rectangle live (bit b of l or bit VC + b: column b); slot kWdTile only while the corner product does
+  auto wave_slots = [&](uint32_t l, uint32_t w, uint32_t wa, uint32_t vs0) -> uint32_t {
+    uint32_t s = wide_slots_needed<VC>(l, wa, vs0);
+    if constexpr (VC == 3) {
+      if (corner && (w == kWdDiagCornerWave) && l) {
+        s = (s & ~(1u << (vs0 + kWdDiagCornerCol))) | (((l >> kWdDiagCornerCol) & 1u) << kWdTile);
+      }
+    }
+    return s;
+  };
   // row-block slots the workgroup reads: the rectangles of the waves that own a live product
   uint32_t wg_need = 0;
 #ifdef LDP_MEASURE
@@ -411,14 +441,25 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
 #pragma unroll
   for (uint32_t w = 0; w < static_cast<uint32_t>(kWdWaves); ++w) {
     const uint32_t wa = rect_a0(w), wb = rect_b0(w);
-    const uint32_t wl = ((mask_row(wa) | mask_row(wa + 1)) >> wb) & rect_own(w);
+    uint32_t wl = ((mask_row(wa) | mask_row(wa + 1)) >> wb) & rect_own(w);
+    if constexpr (VC == 3) {
+      wl |= (corner && (w == kWdDiagCornerWave)) ? (1u << kWdDiagCornerCol) : 0u;
+    }
 #ifdef LDP_MEASURE
     m_live_waves += wl ? 1u : 0u;
 #endif
-    wg_need |= wide_slots_needed<VC>(wl, wa, (diag ? 0u : static_cast<uint32_t>(kWdTile)) + wb);
+    wg_need |= wave_slots(wl, w, wa, (diag ? 0u : static_cast<uint32_t>(kWdTile)) + wb);
   }
   wg_need = __builtin_amdgcn_readfirstlane(wg_need);
-  auto slot_first = [&](uint32_t s) { return (s < static_cast<uint32_t>(kWdTile)) ? (jv0 + static_cast<int32_t>(kMfBlock * s)) : (vv0 + static_cast<int32_t>(kMfBlock * (s - kWdTile))); };
+  // (VC == 3, a diagonal tile: its V blocks are slots 0-7, and slot kWdTile is the row-block in FRONT of the tile -- the corner product's; the first tile of
+  // the image has none and never asks for it: the clamps below keep the address legal)
+  const int32_t upper0 = (VC == 3) ? (jv0 - static_cast<int32_t>(kMfBlock)) : vv0;
+  auto slot_first = [&](uint32_t s) { return (s < static_cast<uint32_t>(kWdTile)) ? (jv0 + static_cast<int32_t>(kMfBlock * s)) : (upper0 + static_cast<int32_t>(kMfBlock * (s - kWdTile))); };
+  // a column of this wave's rectangle: its row-block slot and its first variant
+  auto col_slot = [&](uint32_t b) -> uint32_t { return (b == corner_col) ? static_cast<uint32_t>(kWdTile) : (vslot0 + b); };
+  auto col_first = [&](uint32_t b) -> int64_t {
+    return (b == corner_col) ? (static_cast<int64_t>(jv0) - kMfBlock) : (static_cast<int64_t>(vv0) + kMfBlock * (b0 + b));
+  };
 
   // ---- DMA plan: per-lane source offsets (registers) and per-instruction row-block bases (uniform) ----
   // instruction T of a stage = a quarter of row-block slot T >> 2: eight rows x eight 16-byte pieces
@@ -459,9 +500,9 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
 #pragma unroll
   for (int b = 0; b < VC; ++b) {
     const uint32_t slot = vslot0 + b;
-    voff[b] = (((VC == 3) && (slot > 7u)) ? 7u : slot) * kWdBlockUnits;  // (VC == 3, last wave: a block that does not exist is read as block 7 and never live)
+    voff[b] = ((static_cast<uint32_t>(b) == corner_col) ? static_cast<uint32_t>(kWdTile) : (((VC == 3) && (slot > 7u)) ? 7u : slot)) * kWdBlockUnits;  // (VC == 3, last wave: a block that does not exist is read as block 7 and never live)
   }
-  uint32_t need = wide_slots_needed<VC>(live, a0, vslot0);
+  uint32_t need = wave_slots(live, wave, a0, vslot0);
   // window starts of this lane's two second variants (J0 + r, J1 + r), fetched here: the k-loop must not hold ordinary
   // global loads (hipcc would drain the DMA ring in front of every LDS read of the loop)
   uint32_t lo_j2[2] = {0xffffffffu, 0xffffffffu};  // (lo >= j: no candidate pair)
@@ -681,12 +722,13 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
             continue;
           }
           const uint32_t b = p - static_cast<uint32_t>(q) * VC;  // V block of the product
-          const uint32_t vslot = vslot0 + b;
+          const uint32_t vslot = col_slot(b);
+          const int64_t vfirst = col_first(b);
           bool hopeless = true;
 #pragma unroll 2
           for (uint32_t g = 0; g < 16; ++g) {
             const uint32_t row = (g & 3) + 8 * (g >> 2) + 4 * h;
-            const int64_t i64 = static_cast<int64_t>(vv0) + kMfBlock * (b0 + b) + row;
+            const int64_t i64 = vfirst + row;
             if ((i64 >= lo_j) && (i64 < j64)) {
               const cp_slot ci = cpl[(vslot * kMfBlock + row) * 2];
               if constexpr (SPARSE) {
@@ -720,7 +762,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
       keep = __builtin_amdgcn_readfirstlane(keep);
       if (keep != live) {
         live = keep;
-        need = wide_slots_needed<VC>(live, a0, vslot0);
+        need = wave_slots(live, wave, a0, vslot0);
         if (!live) {
           stop_stage = kc;  // the wave computes nothing from here on
         }
@@ -816,7 +858,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
           if (!(live & (1u << (VC * round + pl)))) {
             continue;
           }
-          const int64_t vfirst = static_cast<int64_t>(vv0) + kMfBlock * (b0 + pl) + 4 * h;
+          const int64_t vfirst = col_first(pl) + 4 * h;
 #pragma unroll 1
           for (uint32_t g = 0; g < 16; ++g) {
             const int64_t i64 = vfirst + (g & 3) + 8 * (g >> 2);
@@ -1408,6 +1450,9 @@ hipError_t launch_pair_wide(const PairKernelArgs& a_in, hipStream_t stream, bool
   a.lds_dwords = static_cast<uint32_t>(lds / sizeof(uint32_t));
   if (a.wd_async || sparse) {
     a.wd_diag_split = 0;  // (the diagonal tiles' kernel exists for the barrier kernel on complete data)
+  }
+  if (!a.wd_diag_split) {
+    a.wd_diag_corner = 0;  // (the corner product moves into the 2 x 3 body, nowhere else)
   }
   const uint32_t per_xcd = (a.n_wd_tiles + 7) / 8;
   const dim3 grid(per_xcd * 8), block(kWdWaves * 64);
