@@ -410,6 +410,18 @@ int ldp_get_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, double*
 /* bit-planes of one variant as the kernels see them: hom and ref2het, ceil(founder_ct/32) dwords each */
 int ldp_get_planes(ldp_engine* e, uint32_t variant, uint32_t* hom, uint32_t* ref2het);
 int ldp_get_counters(const ldp_engine* e, ldp_counters* out);
+/* Per-tile routing: prune launches over wide-band subcontigs send every 8 x 8 tile to the kernel its OWN rows call for -- the
+ * complete-data body, the SPARSE tiles (a few missing calls) or the quarter tiles (pair_mfma_tile4_kernel) -- never above the launch's route word,
+ * which ldp_counters keeps reporting.  The tiles of the last run by the class they ran on (tiles with an empty plan mask are not counted) and
+ * the corner products a diagonal tile computed for its neighbour.  All zero when the run did not route its tiles one by one (option
+ * "tile_route" 0, inspection runs, engines without the tile plan on every route). */
+typedef struct ldp_tile_routes {
+  uint64_t tiles_complete;
+  uint64_t tiles_sparse;
+  uint64_t tiles_general;
+  uint64_t corner_products;
+} ldp_tile_routes;
+int ldp_get_tile_routes(const ldp_engine* e, ldp_tile_routes* out);
 
 
 /* ---- genotype file reader (host-side I/O edge; no GPU involved) ---- */

@@ -52,6 +52,10 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
  *                     profiler or an oversubscribed device
  *   "wide_sparse"     0/1: launches whose rows have a few missing calls keep the 8 x 8 tiles of wide-band subcontigs (the tile kernel's
  *                     SPARSE instantiation; default 1); 0 = they fall back to the parallelogram plan as in rounds 2-5
+ *   "tile_route"      0/1: prune launches whose wide-band subcontigs stay on the tile plan on every route decide PER TILE, on the device and from the
+ *                     records of the rows the tile multiplies, which of the three tile kernels runs it: the complete-data body, the SPARSE
+ *                     instantiation or the quarter tiles, never above the launch's route word (default 1); 0 = the word sends
+ *                     every tile of the launch to one kernel, as in rounds 2-6.  Any other value: LDP_ERR_INVALID
  *   "wide_diag_kernel" 0/1: complete-data prune launches run the tiles ON the diagonal (36 live products, to the end of the rows) in eight 2 x 3
  *                     rectangles, a second body of pair_mfma_wide_kernel picked per workgroup (default 1); 0 = 2 x 4 rectangles for every tile
  *   "wide_diag_corner" 0/1: where "wide_diag_kernel" applies, the diagonal tile also computes the one product of its J tile's distance-1 tile that
@@ -90,6 +94,13 @@ int ldp_debug_wide_plan(const ldp_engine* e, uint32_t* tile_count, uint32_t* wor
  * rectangle: J blocks a0, a0 + 1 x V blocks b0 .. b0 + 2), cols (bit b: the wave owns the products of V block b0 + b), then the products
  * it owns as mask bits 0-31 / 32-63 in ldp_debug_wide_plan()'s layout (bit 8 a + b).  capacity_words < 40: LDP_ERR_INVALID. */
 int ldp_debug_wide_diag_map(uint32_t* words, uint64_t capacity_words);
+
+/* The class every tile of the last run ran on ("tile_route"), one byte per tile in the order of ldp_debug_wide_plan(): bits 0-1 the class
+ * (0 complete-data body, 1 SPARSE tiles, 2 quarter tiles), bit 2: the tile -- a diagonal one -- computed the corner product of its
+ * neighbour, bit 3: the tile -- one tile distance from the diagonal -- left its corner product to the diagonal tile; as the tile actually
+ * ran.  LDP_ERR_STATE before a run and after a run that did not route its tiles one by one (ldp_get_tile_routes() is all zero then),
+ * LDP_ERR_INVALID when capacity < tiles. */
+int ldp_debug_tile_classes(ldp_engine* e, uint8_t* out, uint64_t capacity, uint32_t* tile_count);
 
 
 /* ---- synthetic workload (benchmark / test support, not part of the reference seam) ---- */

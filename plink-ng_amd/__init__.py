@@ -85,6 +85,14 @@ class ldp_counters(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class ldp_tile_routes(ctypes.Structure):
+    _fields_ = [("tiles_complete", ctypes.c_uint64), ("tiles_sparse", ctypes.c_uint64), ("tiles_general", ctypes.c_uint64),
+                ("corner_products", ctypes.c_uint64)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 PAIR_STATS_DTYPE = np.dtype([("nm", "<u4"), ("sum1", "<i4"), ("ssq1", "<u4"), ("sum2", "<i4"), ("ssq2", "<u4"), ("dot", "<i4")])
 R2_HIT_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4"), ("r2", "<f8")])
 VARIANT_REC_DTYPE = np.dtype([("nm_ct", "<u4"), ("sum", "<i4"), ("ssq", "<u4"), ("flags", "<u4"), ("n_homref", "<u4"),
@@ -101,7 +109,7 @@ CABI_SYMBOLS = [
     "ldp_pgen_variant_is_multiallelic", "ldp_pgen_provisional_ref", "ldp_pgen_open_indexed", "ldp_set_r_signed", "ldp_set_variants_vcor_cm", "ldp_pgen_read_alleles", "ldp_pgen_read_phased", "ldp_pgen_read_alleles_phased", "ldp_subset_samples", "ldp_phased_row_bytes", "ldp_phased_phase_offset",
     "ldp_debug_set_option", "ldp_pgen_debug_force_portable", "ldp_matrix_pipe_max_founders", "ldp_map_rows", "ldp_release_device", "ldp_debug_wide_plan",
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
-    "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map",
+    "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
 ]
 
 
@@ -236,6 +244,8 @@ def lib():
     L.ldp_comm_destroy.argtypes = [vp]
     L.ldp_comm_destroy.restype = None
     L.ldp_debug_wide_plan.argtypes = [vp, u32p, u32p, ctypes.c_uint64]
+    L.ldp_get_tile_routes.argtypes = [vp, ctypes.POINTER(ldp_tile_routes)]
+    L.ldp_debug_tile_classes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64, u32p]
     L.ldp_debug_wide_diag_map.argtypes = [u32p, ctypes.c_uint64]
     L.ldp_matrix_pipe_max_founders.argtypes = []
     L.ldp_matrix_pipe_max_founders.restype = ctypes.c_uint32
@@ -888,6 +898,22 @@ class LdPruneEngine:
         r2h = np.zeros(w, dtype=np.uint32)
         self._ck(self._L.ldp_get_planes(self._h, variant, _ptr(hom, ctypes.c_uint32), _ptr(r2h, ctypes.c_uint32)))
         return hom, r2h
+
+    def tile_routes(self):
+        """tiles of the last run by the kernel they ran on -- 'tiles_complete', 'tiles_sparse', 'tiles_general' -- and 'corner_products' handed
+        over; all zero when the run did not route its tiles one by one (ldp_get_tile_routes; option 'tile_route')."""
+        c = ldp_tile_routes()
+        self._ck(self._L.ldp_get_tile_routes(self._h, ctypes.byref(c)))
+        return c.asdict()
+
+    def tile_classes(self):
+        """one uint8 per tile of debug_wide_plan() for the last run: bits 0-1 the class (0 complete, 1 sparse, 2 general), bit 2 corner taken,
+        bit 3 corner given (ldp_debug_tile_classes); LdpError(LDP_ERR_STATE) before a run that routed its tiles."""
+        n = ctypes.c_uint32(0)
+        self._ck(self._L.ldp_debug_tile_classes(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        self._ck(self._L.ldp_debug_tile_classes(self._h, _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)))
+        return out[:n.value]
 
     def counters(self):
         c = ldp_counters()

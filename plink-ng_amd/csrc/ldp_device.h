@@ -274,7 +274,11 @@ struct PairKernelArgs {
   // matrix-pipe tiles (launch_pair_mfma); `route` (one word, written by route_kernel from what prepare_kernel saw of the
   // rows converted so far) sends a whole launch to one kernel: kRouteComplete -> pair_mfma_kernel, kRouteSparse -> its
   // interval-epilogue instantiation (4.1d), kRouteGeneral -> pair_mfma_general_kernel; mf_active = 1: the popcount
-  // kernels of the launch only run for non-zero (the general matrix-pipe kernel is off), 2: they never run
+  // kernels of the launch only run for non-zero (the general matrix-pipe kernel is off), 2: they never run.
+  // With wd_tile_route (below) the word still owns the parallelogram workgroups (mf_wgs) and is what the counters report, but
+  // the 8 x 8 tiles of the launch are sent one by one: tile_route_kernel gives every tile the class of its OWN rows, capped by
+  // this word, and each of the three tile kernels reads a copy of the tile array in which the tiles of the
+  // other two classes have an empty mask.
   const MfmaWG* mf_wgs;
   uint32_t n_mf_wgs;
   uint32_t mf_diag_ct;           // the first mf_diag_ct workgroups of mf_wgs are all-diagonal (MfmaWG::pad bit 1): pair_mfma_kernel's DIAGFORM instantiation
@@ -301,6 +305,14 @@ struct PairKernelArgs {
                                  // waves), picked per workgroup (EngineOptions::wide_diag_kernel)
   uint32_t wd_diag_corner;       // ... and take the corner product of the distance-1 tile of their J tile (kWdDiagCornerWave; EngineOptions::wide_diag_corner);
                                  // only with wd_diag_split
+  // per-tile routing (tile_route_kernel, queued behind route_kernel; EngineOptions::tile_route): the routed copies of wd_tiles (launch order) for
+  // pair_mfma_wide_kernel<0, false> and <0, true>, and of wd_tiles_plain (of wd_tiles where that is null) for pair_mfma_tile4_kernel.  The launchers
+  // hand each kernel its copy in wd_tiles / wd_tiles_plain; with the flag set the complete-data tile kernel runs whatever the group word says, the
+  // SPARSE one unless the word is kRouteComplete, the quarter tiles only on kRouteGeneral (a tile's class never exceeds the word).
+  uint32_t wd_tile_route;
+  const MfmaTile* wd_routed_complete;
+  const MfmaTile* wd_routed_sparse;
+  const MfmaTile* wd_routed_general;
 };
 
 constexpr uint32_t kRouteComplete = 0, kRouteSparse = 1, kRouteGeneral = 2;
@@ -335,6 +347,32 @@ struct MissStats {
 hipError_t launch_miss_stats(const ldp_variant_rec* recs, uint32_t n, uint32_t founder_ct, uint32_t miss_high, MissStats* stats, hipStream_t stream);
 hipError_t launch_route(const MissStats* stats, unsigned long long total_limit, unsigned long long high_limit, int allow_sparse, uint32_t* route_out,
                         hipStream_t stream);
+
+// Per-tile routing (ldp_kernels.hip: tile_route_kernel): one wave per tile of a launch group's launch-order array.  The class of a tile is taken from
+// the records of its LIVE rows -- the rows of every J block whose mask row and of every V block whose mask column is non-zero, clipped at jend and n_rows --
+// by route_kernel's rule, and capped by the group's route word.  ix[t] = (index of launch tile t in the plan, i.e. in the plain-order array and in
+// `cls`; index IN THE LAUNCH SLICE of the other tile of its corner hand-over), 0xffffffff = none (padding / no hand-over).
+struct TileRouteArgs {
+  const MfmaTile* tiles;         // the group's launch-order slice
+  uint32_t n_tiles;
+  const uint2* ix;               // [n_tiles]
+  const ldp_variant_rec* recs;
+  uint32_t n_rows;
+  uint32_t founder_ct;
+  const uint32_t* route;         // the group's word
+  double sparse_frac;            // 0: no sparse class (the SPARSE tiles are not part of the launch)
+  uint32_t miss_high;            // rows with more missing calls than this are high rows
+  uint32_t corner;               // the launch hands corner products over (PairKernelArgs::wd_diag_corner)
+  MfmaTile* out_complete;        // [n_tiles], launch order
+  MfmaTile* out_sparse;          // [n_tiles], launch order
+  MfmaTile* out_general;         // general_plain: indexed by plan index - plan_first; else [n_tiles], launch order
+  uint32_t general_plain;
+  uint32_t plan_first;           // plan index of the group's first tile
+  uint8_t* cls;                  // [plan index]: bits 0-1 the class (kRoute*), bit 2 corner taken, bit 3 corner given
+  unsigned long long* counts;    // [0..2] tiles by class, [3] corner products handed over (added to)
+};
+constexpr uint8_t kTileClsTaken = 4, kTileClsGiven = 8;
+hipError_t launch_tile_route(const TileRouteArgs& a, hipStream_t stream);
 
 struct PrepareArgs {
   const uint8_t* geno;           // row 0 = variant `first`
@@ -426,7 +464,14 @@ hipError_t launch_pair_stats_ref(const uint32_t* planes, uint64_t row_dwords, ui
                                  ldp_pair_stats_t* out, hipStream_t stream);
 size_t pair_tiles_lds_bytes(uint32_t max_rows);
 // ev[0..2] (optional): recorded before the complete-data kernel, between it and the missing-calls kernel, and after
-hipError_t launch_pair_mfma(const PairKernelArgs& a, hipStream_t stream, hipEvent_t* ev);
+// side (optional; launches with wd_tile_route): the SPARSE tiles run on s[0] and the quarter tiles on s[1], forked from `stream` at ev[0] and joined before
+// ev[2] -- with a class per tile the three tile kernels hold disjoint tiles of ONE launch, and back to back on one stream each would wait for the last
+// (longest) tile of the one before it
+struct PairSideStreams {
+  hipStream_t s[2];
+  hipEvent_t fork, join[2];
+};
+hipError_t launch_pair_mfma(const PairKernelArgs& a, hipStream_t stream, hipEvent_t* ev, const PairSideStreams* side = nullptr);
 // chrX pairs of the r^2 outputs (ldp_kernels.hip: x_weighted_kernel): the two engines' six integers of every pair of a dense block
 // (row q = second variant row_first + q, column c = first variant col_first + c, c < cols) -> the male-weighted r^2 (or r)
 struct XWeightedArgs {

@@ -65,6 +65,17 @@ void free_device(ldp_engine* e) {
   e->d_wd_tiles = nullptr;
   (void)hipFree(e->d_wd_tiles_plain);
   e->d_wd_tiles_plain = nullptr;
+  for (int c = 0; c < 3; ++c) {
+    (void)hipFree(e->d_wd_routed[c]);
+    e->d_wd_routed[c] = nullptr;
+  }
+  (void)hipFree(e->d_wd_launch_ix);
+  e->d_wd_launch_ix = nullptr;
+  (void)hipFree(e->d_tile_class);
+  e->d_tile_class = nullptr;
+  (void)hipFree(e->d_tile_counts);
+  e->d_tile_counts = nullptr;
+  e->tile_classes_valid = false;
   (void)hipFree(e->d_miss_stats);
   (void)hipFree(e->d_route);
   e->d_mf_wgs = nullptr;
@@ -707,6 +718,10 @@ void build_shard(ldp_engine* e) {
   e->mf_enabled = e->opt.pair_mfma && (!e->matrix_mode) && (!e->band_r2_mode) && (e->P.founder_ct <= kMfMaxFounders);
   e->mf_wgs.clear();
   e->wd_tiles.clear();
+  e->wd_launch_ix.clear();
+  e->wd_route_ok = false;
+  e->tile_classes_valid = false;
+  e->tile_routes = ldp_tile_routes{0, 0, 0, 0};
   // second variants at which a launch group may end: every matrix-pipe workgroup (and every wide-band tile) lies on one side
   std::vector<uint32_t> safe_cut;
   if (e->mf_enabled) {
@@ -842,6 +857,8 @@ void build_shard(ldp_engine* e) {
       }
     }
     e->wd_launch.clear();
+    e->wd_launch_ix.clear();
+    e->wd_route_ok = !e->wd_tiles.empty();
     for (ldp_engine::PairGroup& g : e->groups) {
       g.wl_first = static_cast<uint32_t>(e->wd_launch.size());
       g.wl_ct = 0;
@@ -864,9 +881,17 @@ void build_shard(ldp_engine* e) {
           corner_pad[t + 1 - g.wd_first] = kWdPadCornerTaken;
         }
       }
+      // (per-tile routing, tile_route_kernel: where each launch tile sits in the plan, and -- filled in below -- where the other tile of its hand-over sits in the launch)
+      std::vector<uint32_t> slice_pos(g.wd_ct, 0xffffffffu);
       auto launch_tile = [&](uint32_t t) {
         MfmaTile tl = e->wd_tiles[t];
         tl.pad = corner_pad[t - g.wd_first];
+        if (slice_pos[t - g.wd_first] != 0xffffffffu) {
+          e->wd_route_ok = false;
+        }
+        slice_pos[t - g.wd_first] = static_cast<uint32_t>(e->wd_launch.size()) - g.wl_first;
+        e->wd_launch_ix.push_back(t);
+        e->wd_launch_ix.push_back(0xffffffffu);
         return tl;
       };
       auto chunk = [](size_t n, uint32_t x) { return std::make_pair(n * x / 8, n * (x + 1) / 8); };
@@ -888,9 +913,19 @@ void build_shard(ldp_engine* e) {
         }
         for (; k < per; ++k) {
           e->wd_launch.push_back(empty);
+          e->wd_launch_ix.push_back(0xffffffffu);
+          e->wd_launch_ix.push_back(0xffffffffu);
         }
       }
       g.wl_ct = static_cast<uint32_t>(8 * per);
+      for (uint32_t q = 0; q < g.wd_ct; ++q) {
+        if (slice_pos[q] == 0xffffffffu) {
+          e->wd_route_ok = false;  // (a plan tile the launch does not hold: cannot happen; the routed copies would miss it)
+        } else if (corner_pad[q]) {
+          const uint32_t partner = (corner_pad[q] == kWdPadCornerGiven) ? (q + 1) : (q - 1);
+          e->wd_launch_ix[2 * (static_cast<size_t>(g.wl_first) + slice_pos[q]) + 1] = slice_pos[partner];
+        }
+      }
     }
   }
   e->load_tag.assign(local, 0);
@@ -998,6 +1033,20 @@ int ensure_device_plan(ldp_engine* e) {
       HIP_TRY(e, hipMalloc(&e->d_wd_tiles_plain, e->wd_tiles.size() * sizeof(MfmaTile)));
       HIP_TRY(e, hipMemcpyAsync(e->d_wd_tiles_plain, e->wd_tiles.data(), e->wd_tiles.size() * sizeof(MfmaTile), hipMemcpyHostToDevice, e->stream));
     }
+    if (e->wd_route_ok && (e->wd_launch_ix.size() == 2 * e->wd_launch.size())) {
+      // the routed copies of the two arrays (tile_route_kernel rewrites a group's slices at every launch of the group), 32 bytes per tile each
+      for (int c = 0; c < 3; ++c) {
+        const size_t tiles = ((c == 2) && e->d_wd_tiles_plain) ? e->wd_tiles.size() : e->wd_launch.size();
+        HIP_TRY(e, hipMalloc(&e->d_wd_routed[c], tiles * sizeof(MfmaTile)));
+        HIP_TRY(e, hipMemsetAsync(e->d_wd_routed[c], 0, tiles * sizeof(MfmaTile), e->stream));
+      }
+      HIP_TRY(e, hipMalloc(&e->d_wd_launch_ix, e->wd_launch.size() * sizeof(uint2)));
+      HIP_TRY(e, hipMemcpyAsync(e->d_wd_launch_ix, e->wd_launch_ix.data(), e->wd_launch.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(e, hipMalloc(&e->d_tile_class, e->wd_tiles.size()));
+      HIP_TRY(e, hipMemsetAsync(e->d_tile_class, 0, e->wd_tiles.size(), e->stream));
+      HIP_TRY(e, hipMalloc(&e->d_tile_counts, 4 * sizeof(unsigned long long)));
+      HIP_TRY(e, hipMemsetAsync(e->d_tile_counts, 0, 4 * sizeof(unsigned long long), e->stream));
+    }
   }
   mark("other hipMallocs + uploads");
   // checkpoints for early termination
@@ -1027,7 +1076,9 @@ int ensure_device_plan(ldp_engine* e) {
     HIP_TRY(e, hipMemsetAsync(e->d_csr_counter, 0, sizeof(unsigned long long), e->stream));
   }
   // (4 counters, then the route words of the launch groups + the inspection launch)
-  HIP_TRY(e, hipHostMalloc(&e->h_counters_pin, 4 * sizeof(unsigned long long) + (e->groups.size() + 1) * sizeof(uint32_t), hipHostMallocDefault));
+  // (4 counters, the groups' route words, and -- from the next 8-byte boundary, tile_counts_pin() -- the 4 per-tile routing counts)
+  HIP_TRY(e, hipHostMalloc(&e->h_counters_pin, (tile_counts_pin_offset(e) + 4) * sizeof(unsigned long long), hipHostMallocDefault));
+  memset(e->h_counters_pin, 0, (tile_counts_pin_offset(e) + 4) * sizeof(unsigned long long));
   mark("pinned host buffers");
   if (e->local_ct) {
     HIP_TRY(e, hipMemcpyAsync(e->d_lo, e->lo_local.data(), e->local_ct * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
@@ -1283,6 +1334,17 @@ void ldp_destroy(ldp_engine* e) {
       if (e->pair_stream[k]) {
         (void)hipStreamDestroy(e->pair_stream[k]);
       }
+    }
+    for (int q = 0; q < 2; ++q) {
+      if (e->tile_side.s[q]) {
+        (void)hipStreamDestroy(e->tile_side.s[q]);
+      }
+      if (e->tile_side.join[q]) {
+        (void)hipEventDestroy(e->tile_side.join[q]);
+      }
+    }
+    if (e->tile_side.fork) {
+      (void)hipEventDestroy(e->tile_side.fork);
     }
   }
   delete e;
@@ -1630,6 +1692,11 @@ int ldp_debug_set_option(ldp_engine* e, const char* name, double value) {
       return fail(e, LDP_ERR_STATE, "csr_capacity must be set before ldp_set_variants()");
     }
     e->opt.csr_capacity = static_cast<uint64_t>(std::max(0.0, value));
+  } else if (n == "tile_route") {
+    if ((value != 0.0) && (value != 1.0)) {
+      return fail(e, LDP_ERR_INVALID, "tile_route must be 0 or 1");
+    }
+    e->opt.tile_route = (value != 0.0);
   } else if (n == "wide_diag_kernel") {
     e->opt.wide_diag_kernel = (value != 0.0);
   } else if (n == "wide_diag_corner") {
@@ -1865,6 +1932,33 @@ int ldp_get_planes(ldp_engine* e, uint32_t variant, uint32_t* hom, uint32_t* ref
     hom[p] = row[off];
     ref2het[p] = row[off + kChunkDwords];
   }
+  return LDP_OK;
+}
+
+int ldp_get_tile_routes(const ldp_engine* e, ldp_tile_routes* out) {
+  if (!e || !out) {
+    return LDP_ERR_INVALID;
+  }
+  *out = e->tile_routes;
+  return LDP_OK;
+}
+
+int ldp_debug_tile_classes(ldp_engine* e, uint8_t* out, uint64_t capacity, uint32_t* tile_count) {
+  if (!e || !tile_count) {
+    return LDP_ERR_INVALID;
+  }
+  if (!e->planned || !e->tile_classes_valid || !e->d_tile_class) {
+    return fail(e, LDP_ERR_STATE, "no run has routed its tiles one by one (ldp_run() with option tile_route 1 on the tile plan)");
+  }
+  *tile_count = static_cast<uint32_t>(e->wd_tiles.size());
+  if (!out) {
+    return LDP_OK;
+  }
+  if (capacity < e->wd_tiles.size()) {
+    return fail(e, LDP_ERR_INVALID, "capacity smaller than the tile count");
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipMemcpy(out, e->d_tile_class, e->wd_tiles.size(), hipMemcpyDeviceToHost));  // (the run that wrote them has been synchronised)
   return LDP_OK;
 }
 

@@ -198,6 +198,8 @@ struct EngineOptions {
   bool wide_diag_corner = true;  // option "wide_diag_corner" 0: the distance-1 tile keeps its corner product (J block 0, V block 7); 1: the diagonal tile of the same J tile
                                  // computes it (ldp_device.h: kWdDiagCornerWave).  Honoured where wide_diag_kernel is
   bool wide_sparse = true;     // LDP_WIDE_SPARSE=0 / option "wide_sparse" 0: launches with a few missing calls leave the 8 x 8 tiles for the parallelogram plan (rounds 2-5)
+  bool tile_route = true;      // option "tile_route" 0: every 8 x 8 tile of a launch group runs on the kernel the group's route word names (rounds 2-6); 1: each tile on
+                               // the kernel its own rows call for, capped by the word (tile_route_kernel)
   bool wide_async = false;     // option "wide_async": the 8 x 8 tiles on pair_mfma_wide_async_kernel (flags instead of a workgroup barrier per stage)
   // test hooks (ldp_debug_set_option only; 0 = off): results never depend on them
   uint32_t replay_steps = 0;   // "replay_steps" k: ldp_debug_replay_pairs() walks every subcontig in k instalments, as the streaming replay of a run does
@@ -261,6 +263,7 @@ struct ldp_engine {
     uint32_t wl_first = 0, wl_ct = 0;    // ... in launch order (wd_launch: eight XCD streams, padded to equal length)
     bool four_tiles = false;             // the group's last launch queued pair_mfma_tile4_kernel for them
     bool sparse_tiles = false;           // ... and pair_mfma_wide_kernel<., SPARSE> (the tiles on the route of rows with a few missing calls)
+    bool tile_routed = false;            // ... with a class per tile (tile_route_kernel)
     bool launched = false;
     hipEvent_t ev_ready = nullptr;
     hipEvent_t ev_done = nullptr;         // kernels finished and the group's predicate words are back on the host
@@ -273,6 +276,7 @@ struct ldp_engine {
   std::vector<MfmaWG> mf_wgs;
   std::vector<MfmaTile> wd_tiles;         // the 8 x 8 tile plan of the wide-band subcontigs (ldp_pair_wide.hip), in J order
   std::vector<MfmaTile> wd_launch;        // the same tiles as the device gets them: per launch group eight XCD streams (see build_shard)
+  std::vector<uint32_t> wd_launch_ix;     // two words per launch tile: d_wd_launch_ix
   uint64_t mf_products = 0;               // 32 x 32 block products of the plan
   uint32_t next_group = 0;                 // groups before this one are launched for the current load epoch
   uint32_t loaded_prefix = 0;              // local variants [0, loaded_prefix) were loaded in the current epoch
@@ -310,6 +314,17 @@ struct ldp_engine {
   MfmaWG* d_mf_wgs = nullptr;
   MfmaTile* d_wd_tiles = nullptr;          // wd_launch
   MfmaTile* d_wd_tiles_plain = nullptr;    // wd_tiles (J order), when the two differ
+  // per-tile routing (tile_route_kernel): the three tile kernels' routed copies of d_wd_tiles ([0] complete, [1] sparse: launch order) and of d_wd_tiles_plain
+  // ([2] general: plain order; launch order where d_wd_tiles_plain is null), rewritten by every launch of a group
+  MfmaTile* d_wd_routed[3] = {nullptr, nullptr, nullptr};
+  uint2* d_wd_launch_ix = nullptr;         // per launch tile: (plan index, launch-slice index of its corner partner); TileRouteArgs::ix
+  uint8_t* d_tile_class = nullptr;         // per plan tile: the class it last ran on + corner bits (ldp_debug_tile_classes)
+  unsigned long long* d_tile_counts = nullptr;  // [4]: tiles by class and corner products handed over, of the launches since reset_launch_counters
+  PairSideStreams tile_side = {{nullptr, nullptr}, nullptr, {nullptr, nullptr}};  // the SPARSE and the quarter tiles of a routed launch run beside the complete-data kernels (created at the first such launch)
+  bool tile_side_ok = false;
+  bool wd_route_ok = false;                // every plan tile of a group appears exactly once in its launch slice (build_shard)
+  bool tile_classes_valid = false;         // the last run routed its tiles one by one: d_tile_class describes it
+  ldp_tile_routes tile_routes = {0, 0, 0, 0};  // ... and these are its counts (all zero otherwise)
   MissStats* d_miss_stats = nullptr;       // [slot of d_route]: missing calls of the resident rows a launch reads (summed from the records when the launch is queued)
   uint32_t* d_route = nullptr;             // [g]: which matrix-pipe kernel owns launch group g (route_kernel, when the group is queued); [groups]: other launches
   uint32_t checkpoint_chunk[kCheckpoints];
@@ -376,6 +391,7 @@ struct ldp_engine {
 };
 
 namespace ldph LDP_HIDDEN {
+hipError_t create_stream(hipStream_t* out, bool high_priority);
 int fail(ldp_engine* e, int code, const std::string& msg);
 int hipfail(ldp_engine* e, hipError_t rc, const char* what);
 
@@ -448,6 +464,8 @@ int finish_removed(ldp_engine* e, const std::vector<uint32_t>& R, uint64_t* remo
 int prepare_mf(ldp_engine* e, std::vector<double>* scratch, const double** mf_out);
 void fill_pair_args(const ldp_engine* e, PairKernelArgs* out, bool with_early_exit);
 int begin_load_epoch(ldp_engine* e);
+// where the per-tile routing counts sit in h_counters_pin (in 8-byte words): behind the 4 counters and the groups' route words
+inline size_t tile_counts_pin_offset(const ldp_engine* e) { return 4 + ((e->groups.size() + 1) * sizeof(uint32_t) + 7) / 8; }
 hipError_t queue_route(ldp_engine* e, size_t slot, hipStream_t stream, int allow_sparse, uint32_t row_end);
 int launch_ready_groups(ldp_engine* e);
 }  // namespace ldph

@@ -398,6 +398,10 @@ void fill_pair_args(const ldp_engine* e, PairKernelArgs* out, bool with_early_ex
   A.wd_sparse = 0;
   A.wd_diag_split = 0;
   A.wd_diag_corner = 0;
+  A.wd_tile_route = 0;
+  A.wd_routed_complete = nullptr;
+  A.wd_routed_sparse = nullptr;
+  A.wd_routed_general = nullptr;
 }
 
 // the dense predicate rows on the host: pinned, allocated the first time a run wants them
@@ -412,6 +416,9 @@ inline bool use_pred_csr(const ldp_engine* e) { return e->opt.pred_csr && (e->h_
 // a new series of pair launches begins: the device-side counters they add to
 int reset_launch_counters(ldp_engine* e) {
   HIP_TRY(e, hipMemsetAsync(e->d_counters, 0, 4 * sizeof(unsigned long long), e->stream));
+  if (e->d_tile_counts) {
+    HIP_TRY(e, hipMemsetAsync(e->d_tile_counts, 0, 4 * sizeof(unsigned long long), e->stream));
+  }
   if (e->d_csr_counter) {
     HIP_TRY(e, hipMemsetAsync(e->d_csr_counter, 0, sizeof(unsigned long long), e->stream));
     HIP_TRY(e, hipMemsetAsync(e->h_csr_flag, 0, sizeof(uint32_t), e->stream));  // (pinned host memory, cleared in stream order)
@@ -509,13 +516,53 @@ int launch_group(ldp_engine* e, uint32_t gi) {
     A.wd_diag_split = (e->opt.wide_diag_kernel && !e->opt.wide_async && A.n_wd_tiles && !A.stats && !A.r2_out && !A.r2_hits && e->wd_diag_lower) ? 1u : 0u;
     A.wd_diag_corner = (A.wd_diag_split && e->opt.wide_diag_corner) ? 1u : 0u;
     g.sparse_tiles = (A.wd_sparse != 0);
+    // A class per TILE (tile_route_kernel) where the tile plan covers its subcontigs on every route the word can take -- the quarter tiles on
+    // kRouteGeneral, the SPARSE tiles on kRouteSparse unless that route is off: anywhere else a tile on the complete-data body would meet the parallelogram
+    // workgroups of its subcontig on another kernel, and pairs would be decided twice.  (wd_general already excludes stats / r2_out / r2_hits.)
+    g.tile_routed = e->opt.tile_route && A.wd_general && (A.wd_sparse || !A.sparse_ok) && !A.wd_async && e->wd_route_ok && e->d_wd_routed[0] && e->d_tile_counts;
+    if (g.tile_routed) {
+      TileRouteArgs T;
+      T.tiles = A.wd_tiles;
+      T.n_tiles = A.n_wd_tiles;
+      T.ix = e->d_wd_launch_ix + g.wl_first;
+      T.recs = e->d_recs;
+      T.n_rows = e->local_ct;
+      T.founder_ct = e->P.founder_ct;
+      T.route = A.route;
+      T.sparse_frac = A.wd_sparse ? e->opt.sparse_frac : 0.0;
+      T.miss_high = static_cast<uint32_t>(std::min(2.0 * e->opt.sparse_frac * static_cast<double>(e->P.founder_ct), 4294967295.0));  // (queue_route's)
+      T.corner = A.wd_diag_corner;
+      T.out_complete = e->d_wd_routed[0] + g.wl_first;
+      T.out_sparse = e->d_wd_routed[1] + g.wl_first;
+      T.general_plain = e->d_wd_tiles_plain ? 1u : 0u;
+      T.out_general = e->d_wd_routed[2] + (e->d_wd_tiles_plain ? g.wd_first : g.wl_first);
+      T.plan_first = g.wd_first;
+      T.cls = e->d_tile_class;
+      T.counts = e->d_tile_counts;
+      const hipError_t trc = launch_tile_route(T, ps);  // (behind route_kernel on the pair stream: every row of the group is counted, the word is written)
+      if (trc != hipSuccess) {
+        return hipfail(e, trc, "tile_route_kernel launch");
+      }
+      if (!e->tile_side_ok) {
+        for (int q = 0; q < 2; ++q) {
+          HIP_TRY(e, create_stream(&e->tile_side.s[q], false));
+          HIP_TRY(e, hipEventCreateWithFlags(&e->tile_side.join[q], hipEventDisableTiming));
+        }
+        HIP_TRY(e, hipEventCreateWithFlags(&e->tile_side.fork, hipEventDisableTiming));
+        e->tile_side_ok = true;
+      }
+      A.wd_tile_route = 1;
+      A.wd_routed_complete = T.out_complete;
+      A.wd_routed_sparse = T.out_sparse;
+      A.wd_routed_general = T.out_general;
+    }
   }
   hipError_t krc = launch_pair_tiles(A, e->max_rows, ps, g.ev);
   if (krc != hipSuccess) {
     return hipfail(e, krc, "pair_tiles_kernel launch");
   }
   if (e->mf_enabled) {
-    krc = launch_pair_mfma(A, ps, g.ev + 4);
+    krc = launch_pair_mfma(A, ps, g.ev + 4, (g.tile_routed && e->tile_side_ok) ? &e->tile_side : nullptr);
     if (krc != hipSuccess) {
       return hipfail(e, krc, "pair_mfma_kernel launch");
     }
@@ -607,6 +654,7 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
   bool replayed = false;
   double replay_busy_ms = 0.0;
   unsigned long long h_counters[4] = {0, 0, 0, 0};
+  bool tile_routed = false;  // some launch of this run gave its tiles a class each (launch_group)
   if (stats) {
     // Inspection run: one launch over every item, every pair's integers stored, no early termination.
     // Whatever the side streams hold is waited for and superseded.
@@ -738,6 +786,12 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
     if (e->mf_enabled) {
       HIP_TRY(e, hipMemcpyAsync(e->h_counters_pin + 4, e->d_route, (e->groups.size() + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     }
+    for (const ldp_engine::PairGroup& g : e->groups) {
+      tile_routed = tile_routed || g.tile_routed;
+    }
+    if (tile_routed) {
+      HIP_TRY(e, hipMemcpyAsync(e->h_counters_pin + tile_counts_pin_offset(e), e->d_tile_counts, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    }
     // 2. ... meanwhile the per-variant records come back on the copy stream and the host derives the
     //    major-allele frequencies the replay needs ...
     rc = fetch_recs(e);
@@ -855,6 +909,12 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
   e->ctr.route_complete_launches = route_ct[0];
   e->ctr.route_sparse_launches = route_ct[1];
   e->ctr.route_general_launches = route_ct[2];
+  e->tile_routes = ldp_tile_routes{0, 0, 0, 0};
+  e->tile_classes_valid = tile_routed;
+  if (tile_routed) {
+    const unsigned long long* tc = e->h_counters_pin + tile_counts_pin_offset(e);
+    e->tile_routes = ldp_tile_routes{tc[0], tc[1], tc[2], tc[3]};
+  }
   e->ctr.four_tile_launches = four_tile_launches;
   e->ctr.sparse_tile_launches = sparse_tile_launches;
   e->ctr.ms_replay = replayed ? replay_busy_ms : (t_end - t_replay);  // (time spent replaying, not waiting for groups)

@@ -619,6 +619,114 @@ hipError_t launch_route(const MissStats* stats, unsigned long long total_limit, 
   return hipGetLastError();
 }
 
+// ---- per-tile routing (ldp_device.h: TileRouteArgs) ----
+// What the live rows of one tile miss (every lane of the wave gets the sums): missing calls, rows, rows beyond miss_high.
+struct TileMiss {
+  unsigned long long total;
+  uint32_t rows, high;
+};
+__device__ __forceinline__ TileMiss tile_live_miss(const TileRouteArgs& A, const MfmaTile& t, uint32_t lane) {
+  // bit a: J block a has a product, bit b: V block b has one
+  uint32_t jm = 0, vm = 0;
+#pragma unroll
+  for (int a = 0; a < kWdTile; ++a) {
+    const uint32_t row = static_cast<uint32_t>(t.mask >> (8 * a)) & 0xffu;
+    jm |= row ? (1u << a) : 0u;
+    vm |= row;
+  }
+  if (t.jv == t.vv) {
+    jm |= vm;  // (diagonal: V block b IS J block b; every row once)
+    vm = 0;
+  }
+  const uint32_t row_end = (t.jend < A.n_rows) ? t.jend : A.n_rows;
+  TileMiss m = {0, 0, 0};
+  // two row-blocks at a time: lanes 0-31 slot 2 k, lanes 32-63 slot 2 k + 1 (slots 0-7 the J blocks, 8-15 the V blocks)
+  const uint32_t live = jm | (vm << kWdTile);
+  for (uint32_t k = 0; k < static_cast<uint32_t>(kWdRowBlocks) / 2; ++k) {
+    const uint32_t slot = 2 * k + (lane >> 5);
+    if ((live >> slot) & 1u) {
+      const int64_t row = static_cast<int64_t>((slot < static_cast<uint32_t>(kWdTile)) ? t.jv : t.vv) + kMfBlock * (slot & (kWdTile - 1)) + (lane & 31);
+      if ((row >= 0) && (row < static_cast<int64_t>(row_end))) {
+        const uint32_t miss = A.founder_ct - A.recs[row].nm_ct;
+        m.total += miss;
+        m.rows += 1;
+        m.high += (miss > A.miss_high) ? 1u : 0u;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    m.total += __shfl_xor(m.total, off, 64);
+    m.rows += __shfl_xor(m.rows, off, 64);
+    m.high += __shfl_xor(m.high, off, 64);
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(256) void tile_route_kernel(TileRouteArgs A) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t idx = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per tile
+  if (idx >= A.n_tiles) {
+    return;
+  }
+  const MfmaTile t = A.tiles[idx];
+  const uint2 ix = A.ix[idx];
+  const uint32_t word = *A.route;
+  uint32_t cls = kRouteComplete;
+  bool hand_over = false;
+  if (t.mask) {
+    const bool paired = A.corner && (t.pad & (kWdPadCornerTaken | kWdPadCornerGiven)) && (ix.y < A.n_tiles);
+    if (word != kRouteComplete) {  // (a complete group has complete tiles only: nothing to read)
+      const TileMiss m = tile_live_miss(A, t, lane);
+      if (m.total) {
+        const double rows = static_cast<double>(m.rows);
+        const unsigned long long total_limit = static_cast<unsigned long long>(A.sparse_frac * static_cast<double>(A.founder_ct) * rows);
+        const unsigned long long high_limit = static_cast<unsigned long long>(0.02 * rows);
+        cls = ((A.sparse_frac > 0.0) && (m.total <= total_limit) && (m.high <= high_limit)) ? kRouteSparse : kRouteGeneral;
+      }
+      cls = (cls < word) ? cls : word;
+      // the corner product changes hands only where BOTH tiles of the hand-over run on the complete-data body
+      hand_over = paired && (cls == kRouteComplete) && (tile_live_miss(A, A.tiles[ix.y], lane).total == 0);
+    } else {
+      hand_over = paired;
+    }
+  }
+  if (lane == 0) {
+    MfmaTile out = t;
+    out.pad = hand_over ? (t.pad & (kWdPadCornerTaken | kWdPadCornerGiven)) : 0u;
+    out.mask = (cls == kRouteComplete) ? t.mask : 0ull;
+    A.out_complete[idx] = out;
+    out.pad = 0;
+    out.mask = (cls == kRouteSparse) ? t.mask : 0ull;
+    A.out_sparse[idx] = out;
+    out.mask = (cls == kRouteGeneral) ? t.mask : 0ull;
+    if (!A.general_plain) {
+      A.out_general[idx] = out;
+    }
+    if (ix.x != 0xffffffffu) {
+      if (A.general_plain) {
+        A.out_general[ix.x - A.plan_first] = out;
+      }
+      const bool taken = hand_over && (t.pad & kWdPadCornerTaken);
+      A.cls[ix.x] = static_cast<uint8_t>(cls | (taken ? kTileClsTaken : 0u) | ((hand_over && !taken) ? kTileClsGiven : 0u));
+      if (t.mask) {
+        atomicAdd(A.counts + cls, 1ull);
+        if (taken) {
+          atomicAdd(A.counts + 3, 1ull);
+        }
+      }
+    }
+  }
+}
+
+hipError_t launch_tile_route(const TileRouteArgs& a, hipStream_t stream) {
+  if (!a.n_tiles) {
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(tile_route_kernel, dim3((a.n_tiles + 3) / 4), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_prepare(const PrepareArgs& a, hipStream_t stream) {
   if (!a.n_variants) {
     return hipSuccess;

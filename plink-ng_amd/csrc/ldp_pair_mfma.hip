@@ -1916,11 +1916,12 @@ __global__ __launch_bounds__(T4<JB>::kWaves * 64, 2) void pair_mfma_tile4_kernel
 }
 
 
-hipError_t launch_pair_mfma(const PairKernelArgs& a_in, hipStream_t stream, hipEvent_t* ev) {
+hipError_t launch_pair_mfma(const PairKernelArgs& a_in, hipStream_t stream, hipEvent_t* ev, const PairSideStreams* side) {
   if (!a_in.n_mf_wgs) {
     return hipSuccess;
   }
   PairKernelArgs a = a_in;
+  const bool split = side && a_in.wd_tile_route && a_in.wd_active;  // the routed tiles of the other two classes beside the complete-data kernels, not behind them
   // 64 KiB (+ 8 KiB static) lets two workgroups share a CU; LDP_DEBUG_MFMA_LDS_KB trades that for a deeper ring (tuning aid)
   static const size_t lds = []() {
     size_t bytes = static_cast<size_t>(kMfLdsDwords) * sizeof(uint32_t);
@@ -1936,6 +1937,15 @@ hipError_t launch_pair_mfma(const PairKernelArgs& a_in, hipStream_t stream, hipE
   a.lds_dwords = static_cast<uint32_t>(lds / sizeof(uint32_t));
   if (ev) {
     (void)hipEventRecord(ev[0], stream);
+  }
+  if (split) {
+    hipError_t frc = hipEventRecord(side->fork, stream);
+    for (int k = 0; (k < 2) && (frc == hipSuccess); ++k) {
+      frc = hipStreamWaitEvent(side->s[k], side->fork, 0);
+    }
+    if (frc != hipSuccess) {
+      return frc;
+    }
   }
   // the workgroups of the launch in two runs: [0, mf_diag_ct) all-diagonal ones (single-form kernel), the rest (general forms)
   const uint32_t n_diag = a_in.mf_diag_ct, n_rest = a_in.n_mf_wgs - a_in.mf_diag_ct;
@@ -1976,7 +1986,7 @@ hipError_t launch_pair_mfma(const PairKernelArgs& a_in, hipStream_t stream, hipE
       hipLaunchKernelGGL((pair_mfma_kernel<4, true, false>), dim3(((n_rest + 7) / 8) * 8), dim3(kMfWaves * 64), lds, stream, ar);
     }
     if (a.wd_active && a.wd_sparse) {
-      const hipError_t wrc = launch_pair_wide(a_in, stream, true);  // ... and the wide-band subcontigs' tiles on that route
+      const hipError_t wrc = launch_pair_wide(a_in, split ? side->s[0] : stream, true);  // ... and the wide-band subcontigs' tiles on that route
       if (wrc != hipSuccess) {
         return wrc;
       }
@@ -2015,11 +2025,16 @@ hipError_t launch_pair_mfma(const PairKernelArgs& a_in, hipStream_t stream, hipE
       }();
       PairKernelArgs t4 = a_in;
       t4.lds_dwords = T4<4>::kLdsDwords;
+      if (t4.wd_tile_route) {
+        // the quarter tiles' routed copy: plain order where the launch has that array, launch order otherwise (the word is kRouteGeneral wherever a tile's class is)
+        (t4.wd_tiles_plain ? t4.wd_tiles_plain : t4.wd_tiles) = t4.wd_routed_general;
+      }
       const uint32_t per_xcd = ((a_in.wd_tiles_plain ? a_in.n_wd_tiles_plain : a_in.n_wd_tiles) * T4<4>::kUnits + 7) / 8;
+      hipStream_t t4s = split ? side->s[1] : stream;
       if (gu) {
-        hipLaunchKernelGGL((pair_mfma_tile4_kernel<4, true>), dim3(per_xcd * 8), dim3(T4<4>::kWaves * 64), t4lds, stream, t4);
+        hipLaunchKernelGGL((pair_mfma_tile4_kernel<4, true>), dim3(per_xcd * 8), dim3(T4<4>::kWaves * 64), t4lds, t4s, t4);
       } else {
-        hipLaunchKernelGGL((pair_mfma_tile4_kernel<4, false>), dim3(per_xcd * 8), dim3(T4<4>::kWaves * 64), t4lds, stream, t4);
+        hipLaunchKernelGGL((pair_mfma_tile4_kernel<4, false>), dim3(per_xcd * 8), dim3(T4<4>::kWaves * 64), t4lds, t4s, t4);
       }
     }
     const uint32_t gper_xcd = (g.n_mf_wgs * 8 + 7) / 8;
@@ -2032,6 +2047,17 @@ hipError_t launch_pair_mfma(const PairKernelArgs& a_in, hipStream_t stream, hipE
       }
     } else {
       hipLaunchKernelGGL((pair_mfma_general_kernel<true, false>), dim3(gper_xcd * 8), dim3(kMfWaves * 64), glds, stream, g);
+    }
+  }
+  if (split) {
+    for (int k = 0; k < 2; ++k) {
+      hipError_t jrc = hipEventRecord(side->join[k], side->s[k]);
+      if (jrc == hipSuccess) {
+        jrc = hipStreamWaitEvent(stream, side->join[k], 0);
+      }
+      if (jrc != hipSuccess) {
+        return jrc;
+      }
     }
   }
   if (ev) {

@@ -927,8 +927,9 @@ template <int ABL, bool SPARSE = false>
 __global__ __launch_bounds__(kWdWaves * 64, 2) void pair_mfma_wide_kernel(PairKernelArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ uint32_t s_need[kWdWaves];
-  if (*A.route != (SPARSE ? kRouteSparse : kRouteComplete)) {
-    return;  // complete rows / a few missing calls / many: one kernel family owns a launch (route_kernel); the others leave at once
+  if (A.wd_tile_route ? (SPARSE && (*A.route == kRouteComplete)) : (*A.route != (SPARSE ? kRouteSparse : kRouteComplete))) {
+    return;  // complete rows / a few missing calls / many: one kernel family owns a launch (route_kernel); the others leave at once.  Routed tiles
+             // (tile_route_kernel): wd_tiles is this kernel's copy, where a tile of another class has an empty mask -- and no class lies above the word
   }
   const uint32_t per_xcd = (A.n_wd_tiles + 7) / 8;
   const uint32_t idx = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);  // consecutive tiles on one XCD
@@ -1453,6 +1454,9 @@ hipError_t launch_pair_wide(const PairKernelArgs& a_in, hipStream_t stream, bool
   }
   if (!a.wd_diag_split) {
     a.wd_diag_corner = 0;  // (the corner product moves into the 2 x 3 body, nowhere else)
+  }
+  if (a.wd_tile_route) {
+    a.wd_tiles = sparse ? a.wd_routed_sparse : a.wd_routed_complete;  // (never with wd_async: launch_group)
   }
   const uint32_t per_xcd = (a.n_wd_tiles + 7) / 8;
   const dim3 grid(per_xcd * 8), block(kWdWaves * 64);

@@ -819,6 +819,13 @@ struct PruneJob {
     logprintf("[timing] pair launches by route: complete data %u | a few missing calls %u (%u on the 8 x 8 tiles) | missing calls %u (%u on quarter tiles) | %u tiles planned, %llu pairs recounted exactly\n",
               c.route_complete_launches, c.route_sparse_launches, c.sparse_tile_launches, c.route_general_launches, c.four_tile_launches, c.wide_tiles,
               static_cast<unsigned long long>(c.sparse_exact_pairs));
+    // ... and, where the launches gave every 8 x 8 tile the class of its own rows (ldp_get_tile_routes), the tiles by the kernel they ran on
+    ldp_tile_routes tr;
+    if ((ldp_get_tile_routes(eng[0], &tr) == LDP_OK) && (tr.tiles_complete | tr.tiles_sparse | tr.tiles_general)) {
+      logprintf("[timing] tiles by their own rows: complete data %llu | a few missing calls %llu | missing calls %llu (quarter tiles) | %llu corner products handed over\n",
+                static_cast<unsigned long long>(tr.tiles_complete), static_cast<unsigned long long>(tr.tiles_sparse), static_cast<unsigned long long>(tr.tiles_general),
+                static_cast<unsigned long long>(tr.corner_products));
+    }
   }
 
   // ---- chrX, chrY: their own sample sets, rows built on the host, one engine each on device 0
