@@ -1,13 +1,15 @@
 """CPU tests of the per-pair reference the GPU tests compare the production kernels' decisions with (ldtools.band_pair_stats,
 band_decisions, compare_decisions): plain float64 matrix products and three float64 multiplications, checked here against
 the oracle's word-by-word popcount arithmetic (oracle/ldoracle.c) for EVERY candidate pair of small bands that hold the rows
-kernels go wrong on.  Also the measurement of how much of a single wrong decision the prune set shows."""
+kernels go wrong on, and for every pair of the rows with missing calls that tests/test_r2_missing.py runs the r^2 kernels on
+(r2_tools.missing_rows, whose input conditions are checked here too).  Also the measurement of how much of a single wrong decision the prune set shows."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import ldtools as T
+import r2_tools as R
 from test_host_logic import make_positions, recs_from_vaggs
 
 
@@ -139,6 +141,72 @@ def test_every_r2_of_all_pairs_equals_the_oracle(n):
             w = r2[k] if i < j else (d[j] if i == j else 0.0)
             assert T.bits_of(np.float64(dense[j - 10, i - 5]))[()] == T.bits_of(np.float64(w))[()], (i, j)
     print("pairs compared: %d (r^2, r major-oriented, r REF-oriented, float32 casts)" % len(first))
+
+
+@pytest.mark.parametrize("n", [3, 90, 512, 513, 1100])
+def test_rows_with_missing_calls_meet_their_input_conditions(n):
+    """r2_tools.missing_rows (the fixture of tests/test_r2_missing.py): the placed rows at every n, the counts and shares from n = 90 on --
+    MissingReference.input_conditions, from the reference alone; the smaller matrices of the planner test as well"""
+    ref = R.reference_missing(600, n)
+    ref.input_conditions()
+    places = R.missing_places(600)
+    assert places == {"all_missing": [17, 300, 597], "complementary": [(50, 290), (258, 259), (31, 32)], "shared_variance": [(70, 330), (513, 515)],
+                      "edges": [100, 257, 599], "singletons": [110, 521]}
+    assert R.missing_places(200) == {"all_missing": [17, 197], "complementary": [(31, 32)], "shared_variance": [], "edges": [100, 199], "singletons": [110]}
+    assert np.array_equal(ref.raw, R.missing_rows(600, n)) and not ref.raw.flags.writeable      # one seeded generator: the same rows every time
+    kept = ref.raw != 3
+    unplaced = np.ones(600, dtype=bool)
+    unplaced[[26, 70, 513, 110, 521]] = False                                                             # (rows rewritten as a whole)
+    assert np.array_equal(ref.raw[unplaced][kept[unplaced]], R.complete_rows(600, n)[unplaced][kept[unplaced]])   # every call left is complete_rows' call
+    if n >= 90:
+        c = ref.counts
+        assert c["nm0"] >= 1500 and c["nan_own_variance"] >= 20 and c["strong"] >= 500 and 0.25 <= c["negative"] <= 0.75
+        assert c["complete_rows"] >= 150 and 2 * c["partial"] >= 179700
+    if n == 90:
+        for m in (384, 385, 200):
+            R.reference_missing(m, n).input_conditions()
+
+
+@pytest.mark.parametrize("n", [90, 513])
+def test_reference_of_the_rows_with_missing_calls_equals_the_oracle(n):
+    """band_pair_stats / band_r2 (r^2, r in both orientations) on missing_rows(600, n): EVERY pair's six integers equal the oracle's word-by-word
+    popcounts, every value its cov, var1, var2 through ComputeR2's operations bit for bit -- all-missing rows, pairs without a shared sample,
+    variance that vanishes on the shared samples, major alleles decided by the calls a row has"""
+    m = 600
+    ref = R.reference_missing(m, n)
+    inv, mf, altmaj = T.oracle_prepare(ref.raw)
+    assert np.array_equal(altmaj.astype(bool), R.alt_major(ref.raw))
+    hom, r2h, vaggs = T.oracle_split(inv, n)
+    pairs = len(ref.first)
+    assert pairs == m * (m - 1) // 2
+    want_stats = np.zeros((pairs, 6), dtype=np.int64)
+    cvv = np.zeros((pairs, 3), dtype=np.float64)
+    for k in range(pairs):
+        st = T.oracle_pair_stats(hom, r2h, vaggs, n, int(ref.first[k]), int(ref.second[k]))
+        want_stats[k] = st.astuple()
+        cvv[k] = T.oracle_r2(st)
+    bad = np.flatnonzero((ref.stats != want_stats).any(1))
+    assert not len(bad), [(int(ref.first[k]), int(ref.second[k]), ref.stats[k].tolist(), want_stats[k].tolist()) for k in bad[:5]]
+    cov, prod = cvv[:, 0], cvv[:, 1] * cvv[:, 2]
+    undefined = (want_stats[:, 0] == 0) | (prod == 0.0)
+    want = (cov * cov) / np.where(undefined, 1.0, prod)
+    want_major = np.sqrt(want)
+    want_major[cov < 0] = -want_major[cov < 0]
+    flip = (altmaj[ref.first] ^ altmaj[ref.second]).astype(bool)
+    want_ref = np.where(flip & (want_major != 0.0), -want_major, want_major)
+    for w in (want, want_major, want_ref):
+        T.bits_of(w)[undefined] = T.R2_NAN64
+    for mode, w in ((0, want), (1, want_major), (2, want_ref)):
+        bad = np.flatnonzero(T.bits_of(ref.band[mode]) != T.bits_of(w))
+        assert not len(bad), (mode, [(int(ref.first[k]), int(ref.second[k]), ref.band[mode][k], w[k], want_stats[k].tolist()) for k in bad[:5]])
+    d = ref.diag
+    for v in range(m):
+        st = T.oracle_pair_stats(hom, r2h, vaggs, n, v, v)
+        c, v1, v2 = T.oracle_r2(st)
+        w = np.float64(c * c / (v1 * v2)) if (st.nm and v1 * v2 != 0.0) else np.array([T.R2_NAN64], dtype=np.uint64).view(np.float64)[0]
+        assert T.bits_of(np.float64(d[v]))[()] == T.bits_of(np.float64(w))[()], v
+    assert undefined.sum() >= 1500 and (want_stats[:, 0] == 0).sum() >= 1500 and (undefined & (want_stats[:, 0] > 0)).sum() >= 20
+    print("pairs compared: %d (six integers, r^2, r major-oriented, r REF-oriented), %d undefined" % (pairs, int(undefined.sum())))
 
 
 def test_decisions_from_a_structured_stats_array(pkg):
