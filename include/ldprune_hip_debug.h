@@ -46,10 +46,6 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
  *                     memory (default 1); 0 = the dense rows are copied back whole, as in rounds 1-5
  *   "csr_capacity"    k: (test hook, before ldp_set_variants()) the compacted rows' buffer holds k entries; a run with more non-zero words falls back
  *                     to the dense rows (0 = a quarter of all predicate words)
- *   "wide_async"      0/1: the 8 x 8 tiles on the barrier-free experiment of round 5 (pair_mfma_wide_async_kernel; default 0).  For measurements
- *                     and tests ONLY: a wave whose LDS poll does not come true within ~2^22 polls (a fraction of a second) traps, which ends the
- *                     HIP context of the whole process with no LDP_ERR code -- timing alone can do that under a debugger, a single-stepping
- *                     profiler or an oversubscribed device
  *   "wide_sparse"     0/1: launches whose rows have a few missing calls keep the 8 x 8 tiles of wide-band subcontigs (the tile kernel's
  *                     SPARSE instantiation; default 1); 0 = they fall back to the parallelogram plan as in rounds 2-5
  *   "tile_route"      0/1: prune launches whose wide-band subcontigs stay on the tile plan on every route decide PER TILE, on the device and from the

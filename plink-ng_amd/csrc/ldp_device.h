@@ -298,7 +298,6 @@ struct PairKernelArgs {
   // workgroup, and the deferred order costs it 3 % (config 5's density: 115.1 against 118.3 ms); nullptr: wd_tiles serves both
   const MfmaTile* wd_tiles_plain;
   uint32_t n_wd_tiles_plain;
-  uint32_t wd_async;             // the tiles run on pair_mfma_wide_async_kernel (no workgroup barrier in the stage loop; EngineOptions::wide_async)
   uint32_t wd_sparse;            // the tiles also own the launch on the kRouteSparse route (pair_mfma_wide_kernel<., SPARSE>; EngineOptions::wide_sparse):
                                  // pair_mfma_kernel<., SPARSE = true> then skips the workgroups of their subcontigs as the complete-data kernel does
   uint32_t wd_diag_split;        // complete-data prune launches: the tiles on the diagonal take the kernel's 2 x 3 body (kWdDiagMap: 2 x 3 rectangles on all eight

@@ -394,7 +394,6 @@ void fill_pair_args(const ldp_engine* e, PairKernelArgs* out, bool with_early_ex
   A.wd_active = 0;
   A.wd_tiles_plain = nullptr;
   A.n_wd_tiles_plain = 0;
-  A.wd_async = e->opt.wide_async ? 1u : 0u;
   A.wd_sparse = 0;
   A.wd_diag_split = 0;
   A.wd_diag_corner = 0;
@@ -513,13 +512,13 @@ int launch_group(ldp_engine* e, uint32_t gi) {
     // ... and launches whose rows have only a few: the tiles' SPARSE instantiation
     A.wd_sparse = (A.sparse_ok && e->opt.wide_sparse && A.n_wd_tiles) ? 1u : 0u;
     // complete data: the diagonal tiles in 2 x 3 rectangles, by a kernel of their own (prune launches: their live products lie on and below the diagonal)
-    A.wd_diag_split = (e->opt.wide_diag_kernel && !e->opt.wide_async && A.n_wd_tiles && !A.stats && !A.r2_out && !A.r2_hits && e->wd_diag_lower) ? 1u : 0u;
+    A.wd_diag_split = (e->opt.wide_diag_kernel && A.n_wd_tiles && !A.stats && !A.r2_out && !A.r2_hits && e->wd_diag_lower) ? 1u : 0u;
     A.wd_diag_corner = (A.wd_diag_split && e->opt.wide_diag_corner) ? 1u : 0u;
     g.sparse_tiles = (A.wd_sparse != 0);
     // A class per TILE (tile_route_kernel) where the tile plan covers its subcontigs on every route the word can take -- the quarter tiles on
     // kRouteGeneral, the SPARSE tiles on kRouteSparse unless that route is off: anywhere else a tile on the complete-data body would meet the parallelogram
     // workgroups of its subcontig on another kernel, and pairs would be decided twice.  (wd_general already excludes stats / r2_out / r2_hits.)
-    g.tile_routed = e->opt.tile_route && A.wd_general && (A.wd_sparse || !A.sparse_ok) && !A.wd_async && e->wd_route_ok && e->d_wd_routed[0] && e->d_tile_counts;
+    g.tile_routed = e->opt.tile_route && A.wd_general && (A.wd_sparse || !A.sparse_ok) && e->wd_route_ok && e->d_wd_routed[0] && e->d_tile_counts;
     if (g.tile_routed) {
       TileRouteArgs T;
       T.tiles = A.wd_tiles;

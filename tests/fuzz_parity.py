@@ -5,7 +5,7 @@ both scan orders, thresholds from 0.02 to 0.95, missing rates from 0 to 20 %, LD
 rows, several chromosomes.  Compared per case: the prune set with the oracle's, and the decision of EVERY candidate pair (the predicate
 rows of the production run, LdPruneEngine.last_pred) with the float64 reference of ldtools (band_pair_stats / band_decisions).  Prints
 the first mismatching case (seed) and exits non-zero.
-    python tests/fuzz_parity.py [--cases 150] [--seed 1] [--mixed | --wide-missing | --wide-sparse | --wide-async | --r2]
+    python tests/fuzz_parity.py [--cases 150] [--seed 1] [--mixed | --wide-missing | --wide-sparse | --r2]
 --r2: the r^2 outputs of complete-data launches instead (rows, a column block and the hit filter of random all-pairs requests, every value
 bit for bit against ldtools.band_r2; the counters must show the complete route)."""
 import argparse
@@ -22,7 +22,7 @@ import ldtools as T  # noqa: E402
 import __graft_entry__ as ge  # noqa: E402
 
 
-def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=False, mixed=False):
+def one_case(pkg, rng, idx, wide_missing=False, wide_sparse=False, mixed=False):
     n = int(rng.choice([33, 64, 100, 511, 512, 513, 1000, 1536, 2047, 2049, 3000, 5000, 9000]))
     if wide_sparse:
         n = int(rng.choice([1536, 2049, 5000, 9000, 20000, 40000]))   # --wide-sparse: enough 512-sample stages for the checkpoints to fire
@@ -30,8 +30,6 @@ def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=Fa
     miss = float(rng.choice([0.0, 0.0, 0.0, 0.001, 0.003, 0.01, 0.05, 0.2]))
     if wide_sparse:
         miss = float(rng.choice([0.0001, 0.0003, 0.001, 0.002, 0.004, 0.005]))   # ... a FEW missing calls in every row: the tile kernel's SPARSE instantiation
-    if wide_async:
-        miss = 0.0                                    # --wide-async: complete data through the tile plan on the barrier-free kernel
     if wide_missing:
         miss = float(rng.choice([0.01, 0.05, 0.2]))   # --wide-missing: every case on the missing-call kernels ...
     raw = T.synth_raw_codes(m, n, seed=int(rng.integers(1, 1 << 30)), missing_rate=0.0 if mixed else miss)
@@ -79,9 +77,6 @@ def one_case(pkg, rng, idx, wide_missing=False, wide_async=False, wide_sparse=Fa
     wide = int(rng.choice([-1, -1, 0, 1, 3]))  # (drawn for every case, so that the sequence of cases stays the same)
     if wide_missing or wide_sparse:
         wide = int(idx % 3)                        # ... over the tile plan (quarter tiles of the four-product form unless switched off below)
-    if wide_async:
-        wide = int(idx % 3)
-        eng.set_option("wide_async", 1)
     if wide >= 0:
         eng.set_option("wide_min_reach", wide)  # send narrower bands through the 8 x 8 tile plan of the wide-band kernel too
     if idx % 3 == 2:
@@ -196,7 +191,6 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--wide-missing", action="store_true", help="every case has missing calls and takes the wide-band tile plan (pair_mfma_tile4_kernel)")
     ap.add_argument("--wide-sparse", action="store_true", help="every case has a FEW missing calls (0.01-0.5 %%) and takes the tile plan: pair_mfma_wide_kernel's SPARSE instantiation")
-    ap.add_argument("--wide-async", action="store_true", help="every case is complete data on the tile plan, run by pair_mfma_wide_async_kernel (engine option wide_async)")
     ap.add_argument("--mixed", action="store_true", help="the rows' missing rate is drawn per block of rows from {0, 0.1 %%, 5 %%}: mixed-missingness filesets")
     ap.add_argument("--r2", action="store_true", help="the r^2 outputs of complete-data launches (rows, blocks, hits) against ldtools.band_r2")
     args = ap.parse_args()
@@ -215,7 +209,7 @@ def main():
         return
     skipped_any = sparse_tiles = 0
     for k in range(args.cases):
-        ok, desc = one_case(pkg, rng, k, args.wide_missing, args.wide_async, args.wide_sparse, args.mixed)
+        ok, desc = one_case(pkg, rng, k, args.wide_missing, args.wide_sparse, args.mixed)
         if "skipped=0.00" not in desc:
             skipped_any += 1
         if "sparse_tile_launches=0" not in desc:

@@ -182,6 +182,20 @@ def test_parameter_validation(pkg):
     e.close()
 
 
+def test_the_barrier_free_tile_kernel_is_no_option_any_more(pkg):
+    """Round 5's barrier-free tile kernel was removed after its measurement: its option is an unknown name."""
+    e = pkg.LdPruneEngine(100, 50, 5, False, 0.2)
+    with pytest.raises(pkg.LdpError) as ei:
+        e.set_option("wide_async", 1)
+    assert ei.value.code == pkg.LDP_ERR_INVALID
+    e.close()
+
+
+def test_the_product_library_does_not_ship_the_barrier_free_tile_kernel(pkg):
+    """A kernel's mangled name sits in the code object: neither it nor the option's name is in the built library."""
+    assert b"wide_async" not in open(pkg.LIB_PATH, "rb").read()
+
+
 def test_no_cpu_fallback_without_gpu(pkg):
     """The product path must fail loudly when no HIP device is usable."""
     if pkg.device_count() > 0:

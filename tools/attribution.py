@@ -107,8 +107,6 @@ def main():
                 rec["cycles_per_dead_stage_visit"] = (m[3] / m[10]) if m[10] else None
                 rec["wait_plus_barrier_cycles_per_stage_visit"] = ((m[0] + m[1]) / (m[9] + m[10])) if (m[9] + m[10]) else None
                 rec["stage_visits_live_dead"] = [m[9], m[10]]
-                if m[11] or m[12] or m[13]:   # the barrier-free kernel: polls at the top of a stage, deferred DMA issues, s_waitcnt vmcnt of the confirmations
-                    rec["async_frac_of_wave_cycles"] = {"top_poll_and_issue": m[11] / tot, "deferred_issue_poll": m[12] / tot, "confirm_vmcnt": m[13] / tot}
             if m[16]:   # the tiles on the diagonal: how many of the workgroup's eight waves their stages ran on, and the live wave-stages of each SIMD (waves s, s + 4)
                 rec["diag_tiles"] = {"tiles": m[16], "stages": m[17], "stages_le4_live_waves": m[18], "stages_one_live_wave": m[19],
                                      "frac_stages_le4_live_waves": m[18] / m[17] if m[17] else None, "live_wave_stages_per_simd": m[20:24],

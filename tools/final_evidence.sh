@@ -21,7 +21,6 @@ timeout 400 python tests/cli_e2e.py > $O/cli_e2e.txt 2>&1
 timeout 300 python tests/cli_e2e.py --pgen > $O/cli_e2e_pgen.txt 2>&1
 timeout 240 python tests/fuzz_parity.py --cases 400 > $O/fuzz.txt 2>&1
 timeout 240 python tests/fuzz_parity.py --wide-missing --cases 300 > $O/fuzz_wm.txt 2>&1
-timeout 200 python tests/fuzz_parity.py --wide-async --cases 250 > $O/fuzz_async.txt 2>&1
 timeout 240 python tests/fuzz_cli.py --cases 80 > $O/fuzz_cli.txt 2>&1
 timeout 300 python tools/bench_decode.py --out $O/decode.jsonl > $O/decode.log 2>&1
-cat $O/gpu_suite.txt; tail -3 $O/bench_n1.time; tail -c 300 $O/bench_n1.json; tail -n 3 $O/fuzz.txt $O/fuzz_wm.txt $O/fuzz_async.txt $O/fuzz_cli.txt 2>/dev/null | tail -n 12; tail -4 $O/cli_e2e.txt
+cat $O/gpu_suite.txt; tail -3 $O/bench_n1.time; tail -c 300 $O/bench_n1.json; tail -n 3 $O/fuzz.txt $O/fuzz_wm.txt $O/fuzz_cli.txt 2>/dev/null | tail -n 12; tail -4 $O/cli_e2e.txt
