@@ -315,6 +315,24 @@ int ldp_release_device(ldp_engine* e);
  * weights of :2096-2112) when the non-male columns appear twice.  src_sample, het_to_missing: founder_ct entries each.
  * Rows loaded with LDP_GENO_MAPPED are then raw_sample_ct samples wide (ceil(raw_sample_ct / 4) bytes). */
 int ldp_set_sample_map(ldp_engine* e, uint32_t raw_sample_ct, const uint32_t* src_sample, const uint8_t* het_to_missing);
+/* Load first, then drop variants and plan: for a host whose variant filters need the genotype counts (--geno / --maf / --mac: the
+ * records of ldp_get_variant_recs() carry nm_ct, n_homref, n_het, n_homalt of every loaded row), so that the counts the load has
+ * made anyway decide which variants stay.  Create the engine over the candidates with ldp_set_variants_matrix() -- rows, count pass
+ * and records, no band --, load them by any of the load calls, read the records, then call this with
+ *   keep_bitmap    one bit per variant of the engine as it is (variant_ct bits), set = the variant stays,
+ *   kept_ct        the number of bits set,
+ *   chr_idx, bps   of the kept variants in order, as ldp_set_variants() takes them.
+ * Afterwards the engine is the engine ldp_set_variants(kept_ct, chr_idx, bps) and a load of the kept rows alone would have made:
+ * variant k is the k-th kept one; image rows, records, major-allele frequencies (the caller's own, ldp_set_maj_freqs(), and the
+ * derived ones) and preferred bits are found at the new indices, and ldp_run() answers the same.  The image is compacted where it
+ * lies, on the engine's stream, at most one batch of rows (256 MiB) going through a bounce buffer; no second image is allocated,
+ * and the tail of the allocation stays unused until ldp_release_device().  The call returns when the engine is ready.
+ * State: every owned row loaded and no pair work queued -- none is after ldp_set_variants_matrix(); on a windowed plan loads from
+ * host memory queue pair work as they go, and ldp_run() always has -- otherwise LDP_ERR_STATE and nothing is changed.  The call
+ * may be repeated on the restricted engine (filters compose).  kept_ct == variant_ct moves no row; kept_ct of 0 or 1 leaves an
+ * engine whose ldp_run() removes nothing.  LDP_ERR_UNSUPPORTED on a sharded engine (ldp_set_shard() with world > 1), after
+ * LDP_GENO_PHASED loads and after loads through a sample map that is not a plain subset of the file's samples. */
+int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t kept_ct, const uint32_t* chr_idx, const uint32_t* bps);
 /* major-allele frequencies (GetAlleleFreq(..., maj_alleles[v]), plink2_ld.cc:915) for LDP_GENO_INVERSE
  * input; for REF/BED input the engine derives them itself and this call overrides them. */
 int ldp_set_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, const double* maj_freqs);

@@ -68,6 +68,8 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
  *   "decode_rows"     k: ldp_load_pgen_records*() decode in launches of k rows (LD chains cut everywhere)
  *   "decode_no_lds"   0/1: decoded rows are assembled in global memory (what rows beyond 128 KiB take) instead of LDS
  *   "x_rows"          k: ldp_r2_unphased_block_x*() work in chunks of k rows
+ *   "compact_batch_rows" k: ldp_restrict_variants() moves the image in batches of k rows (0 = as many as 256 MiB hold): which batches
+ *                     are copied directly and which go through the bounce buffer depends on rows per batch
  * Results never depend on these.  Unknown name: LDP_ERR_INVALID. */
 int ldp_debug_set_option(ldp_engine* e, const char* name, double value);
 /* The .pgen reader's phase / subset routines use pext / pdep where the host has BMI2; on != 0 forces the portable loops for the whole
@@ -98,6 +100,11 @@ int ldp_debug_wide_diag_map(uint32_t* words, uint64_t capacity_words);
  * LDP_ERR_INVALID when capacity < tiles. */
 int ldp_debug_tile_classes(ldp_engine* e, uint8_t* out, uint64_t capacity, uint32_t* tile_count);
 
+
+/* What the last ldp_restrict_variants() moved: image rows in all, of them copied directly / through the bounce buffer (a row that
+ * stays where it is counts nowhere), and the device time of the image's compaction (HIP events on the engine's stream).  Any
+ * pointer may be NULL. */
+int ldp_debug_get_compact_stats(const ldp_engine* e, uint64_t* rows_compacted, uint64_t* rows_direct, uint64_t* rows_bounced, double* ms_compact);
 
 /* ---- synthetic workload (benchmark / test support, not part of the reference seam) ---- */
 /* Deterministic genotype generator for the SURVEY.md 8(d) workload: rows [first_variant, +n_variants) of

@@ -110,12 +110,13 @@ CABI_SYMBOLS = [
     "ldp_debug_set_option", "ldp_pgen_debug_force_portable", "ldp_matrix_pipe_max_founders", "ldp_map_rows", "ldp_release_device", "ldp_debug_wide_plan",
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
+    "ldp_restrict_variants", "ldp_debug_get_compact_stats",
 ]
 
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ("ldp_kernels.hip", "ldp_codes.hip", "ldp_pair_mfma.hip", "ldp_pair_wide.hip", "ldp_pred_csr.hip", "ldp_pgen_decode.hip", "ldp_synth.hip", "ldp_engine.cpp", "ldp_engine_run.cpp", "ldp_engine_r2.cpp",
-                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_pgen.cpp", "ldp_topology.cpp")]
+                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_pgen.cpp", "ldp_topology.cpp")]
 
 
 def _stale(target, deps):
@@ -130,7 +131,7 @@ def build_library(force=False, verbose=False, measure=False):
     without a GPU).  In-tree so the .so travels with the repo snapshot.  One object per source under lib/_obj/, stale ones
     recompiled in parallel, then one link.  measure=True: the measurement build, lib/libldprune_hip_measure.so (-DLDP_MEASURE)."""
     headers = [os.path.join(CSRC, "ldp_device.h"), os.path.join(CSRC, "ldp_pair_device.h"), os.path.join(CSRC, "ldp_mfma_device.h"),
-               os.path.join(CSRC, "ldp_env.h"), os.path.join(CSRC, "ldp_engine_internal.h"),
+               os.path.join(CSRC, "ldp_env.h"), os.path.join(CSRC, "ldp_engine_internal.h"), os.path.join(CSRC, "ldp_compact_schedule.h"),
                os.path.join(REPO, "include", "ldprune_hip.h"), os.path.join(REPO, "include", "ldprune_hip_debug.h")]
     headers = [h for h in headers if os.path.exists(h)]
     lib_path = MEASURE_LIB_PATH if measure else LIB_PATH
@@ -228,6 +229,8 @@ def lib():
     L.ldp_debug_get_pred.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64, u64p]
     L.ldp_map_rows.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp), u64p]
     L.ldp_release_device.argtypes = [vp]
+    L.ldp_restrict_variants.argtypes = [vp, u64p, ctypes.c_uint32, u32p, u32p]
+    L.ldp_debug_get_compact_stats.argtypes = [vp, u64p, u64p, u64p, f64p]
     L.ldp_load_pgen_records.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
                                         ctypes.POINTER(ldp_pgen_rec), ctypes.c_uint32, u32p]
     L.ldp_load_pgen_records_phased.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
@@ -771,6 +774,35 @@ class LdPruneEngine:
         out = np.zeros((self.variant_ct + 63) // 64 + 1, dtype=np.uint64)
         self._ck(self._L.ldp_stitch_removed_segments(self._h, _ptr(segs, ctypes.c_uint64), _ptr(out, ctypes.c_uint64)))
         return out
+
+    def restrict_variants(self, keep_mask, chr_idx, bps=None):
+        """ldp_restrict_variants: keep the variants whose keep_mask entry is true (one bool per variant of the engine as it is) and plan
+        again over them -- chr_idx / bps of the kept variants, as set_variants() takes them.  Every row must be loaded and no pair work
+        queued: create the engine with set_variants_matrix(), load, read variant_recs(), then call this.  Afterwards variant k is the k-th
+        kept one."""
+        keep = np.asarray(keep_mask, dtype=bool)
+        assert len(keep) == self.variant_ct
+        chr_idx = _u32(chr_idx)
+        kept_ct = int(keep.sum())
+        assert len(chr_idx) == kept_ct
+        bits = np.packbits(keep, bitorder="little")
+        buf = np.zeros(((self.variant_ct + 63) // 64 + 1) * 8, dtype=np.uint8)
+        buf[:len(bits)] = bits
+        bp_ptr = None
+        if bps is not None:
+            bps = _u32(bps)
+            assert len(bps) == kept_ct
+            bp_ptr = _ptr(bps, ctypes.c_uint32)
+        self._ck(self._L.ldp_restrict_variants(self._h, _ptr(buf.view(np.uint64), ctypes.c_uint64), kept_ct, _ptr(chr_idx, ctypes.c_uint32), bp_ptr))
+        self.variant_ct = kept_ct
+
+    def compact_stats(self):
+        """what the last restrict_variants() moved: 'rows_compacted', of them 'rows_direct' / 'rows_bounced', and 'ms_compact', the device
+        time of the image's compaction (ldp_debug_get_compact_stats)."""
+        n, d, b = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        ms = ctypes.c_double()
+        self._ck(self._L.ldp_debug_get_compact_stats(self._h, ctypes.byref(n), ctypes.byref(d), ctypes.byref(b), ctypes.byref(ms)))
+        return {"rows_compacted": int(n.value), "rows_direct": int(d.value), "rows_bounced": int(b.value), "ms_compact": float(ms.value)}
 
     def release_device(self):
         """Free the engine's device memory, keep its plan (ldp_release_device)."""

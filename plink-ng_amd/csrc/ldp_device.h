@@ -407,6 +407,11 @@ hipError_t launch_codes(const PrepareArgs& a, hipStream_t stream);
 // arbitrary pairs from the code image (the integers in major-allele orientation, like launch_pair_stats_ref)
 // image rows [0, n) with stored_inv[v] != 0 back to the input's orientation, flags cleared (ldp_map_rows: the caller is about to see / rewrite them)
 hipError_t launch_unflip_rows(uint8_t* codes, uint64_t code_row_bytes, uint8_t* stored_inv, uint32_t n, hipStream_t stream);
+// ldp_compact.hip (ldp_restrict_variants): rows of row_bytes bytes (a multiple of 16), destination row dst_row0 + r <- source row
+// (src_idx ? src_idx[r] : r) for r < n_rows; the rows written and the rows read by ONE launch must not overlap (ldp_compact_schedule.h)
+hipError_t launch_compact_rows(void* dst, const void* src, uint64_t row_bytes, const uint32_t* src_idx, uint64_t dst_row0, uint32_t n_rows, hipStream_t stream);
+// ... and one-byte row flags, out of place: dst[k] = src[src_idx[k]], k < n
+hipError_t launch_gather_bytes(uint8_t* dst, const uint8_t* src, const uint32_t* src_idx, uint32_t n, hipStream_t stream);
 hipError_t launch_pair_stats_ref_codes(const uint8_t* codes, uint64_t code_row_bytes, const ldp_variant_rec* recs, const uint32_t* first, const uint32_t* second,
                                        uint32_t n_pairs, ldp_pair_stats_t* out, hipStream_t stream);
 constexpr double kSmallEpsilon = 0.00000000000005684341886080801486968994140625;  // 2^-44 (plink2_float.h:119)

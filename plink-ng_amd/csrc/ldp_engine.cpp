@@ -41,15 +41,21 @@ int hipfail(ldp_engine* e, hipError_t rc, const char* what) {
   return fail(e, LDP_ERR_GPU, std::string(what) + ": " + hipGetErrorString(rc));
 }
 
-void free_device(ldp_engine* e) {
+void free_device(ldp_engine* e, bool keep_image) {
   if (!e->gpu_ok) {
     return;
   }
-  (void)hipFree(e->d_planes);
-  (void)hipFree(e->d_codes);
-  e->d_codes = nullptr;
-  (void)hipFree(e->d_map_mask);
-  e->d_map_mask = nullptr;
+  if (!keep_image) {
+    (void)hipFree(e->d_planes);
+    e->d_planes = nullptr;
+    (void)hipFree(e->d_codes);
+    e->d_codes = nullptr;
+    (void)hipFree(e->d_map_mask);
+    e->d_map_mask = nullptr;
+    (void)hipFree(e->d_stored_inv);
+    e->d_stored_inv = nullptr;
+    e->cp_frozen = false;
+  }
   (void)hipFree(e->d_recs);
   (void)hipFree(e->d_lo);
   (void)hipFree(e->d_row_off);
@@ -98,8 +104,6 @@ void free_device(ldp_engine* e) {
   }
   (void)hipFree(e->d_csr_counter);
   e->d_csr_counter = nullptr;
-  (void)hipFree(e->d_stored_inv);
-  e->d_stored_inv = nullptr;
   if (e->h_counters_pin) {
     (void)hipHostFree(e->h_counters_pin);
     e->h_counters_pin = nullptr;
@@ -108,13 +112,13 @@ void free_device(ldp_engine* e) {
     (void)hipHostUnregister(e->recs.data());
     e->recs_registered = false;
   }
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; (k < 2) && !keep_image; ++k) {
     if (e->h2d_stream[k]) {
       (void)hipStreamDestroy(e->h2d_stream[k]);
       e->h2d_stream[k] = nullptr;
     }
   }
-  for (uint32_t k = 0; k < kStageSlots; ++k) {
+  for (uint32_t k = 0; (k < kStageSlots) && !keep_image; ++k) {
     if (e->h_stage[k]) {
       (void)hipHostFree(e->h_stage[k]);
       (void)hipFree(e->d_stage[k]);
@@ -128,28 +132,30 @@ void free_device(ldp_engine* e) {
       e->copied[k] = nullptr;
     }
   }
-  for (int k = 0; k < 8; ++k) {
-    (void)hipFree(e->dec.ptr[k]);
-    e->dec.ptr[k] = nullptr;
-    e->dec.cap[k] = 0;
-  }
-  (void)hipFree(e->d_ld_base);
-  e->d_ld_base = nullptr;
-  e->ld_base_cap = 0;
   e->ld_base_valid = false;
-  if (e->h_dec_pin) {
-    (void)hipHostFree(e->h_dec_pin);
-    e->h_dec_pin = nullptr;
-    e->dec_pin_cap = 0;
+  if (!keep_image) {
+    for (int k = 0; k < 8; ++k) {
+      (void)hipFree(e->dec.ptr[k]);
+      e->dec.ptr[k] = nullptr;
+      e->dec.cap[k] = 0;
+    }
+    (void)hipFree(e->d_ld_base);
+    e->d_ld_base = nullptr;
+    e->ld_base_cap = 0;
+    if (e->h_dec_pin) {
+      (void)hipHostFree(e->h_dec_pin);
+      e->h_dec_pin = nullptr;
+      e->dec_pin_cap = 0;
+    }
+    (void)hipFree(e->d_sample_map);
+    (void)hipFree(e->d_gather);
+    (void)hipFree(e->d_extra_het);
+    e->d_sample_map = nullptr;
+    e->d_gather = nullptr;
+    e->d_extra_het = nullptr;
+    e->gather_bytes = 0;
+    e->extra_het_cap = 0;
   }
-  (void)hipFree(e->d_sample_map);
-  (void)hipFree(e->d_gather);
-  (void)hipFree(e->d_extra_het);
-  e->d_sample_map = nullptr;
-  e->d_gather = nullptr;
-  e->d_extra_het = nullptr;
-  e->gather_bytes = 0;
-  e->extra_het_cap = 0;
   if (e->prep_ev0) {
     (void)hipEventDestroy(e->prep_ev0);
     (void)hipEventDestroy(e->prep_ev1);
@@ -181,7 +187,6 @@ void free_device(ldp_engine* e) {
   e->next_group = 0;
   e->loaded_prefix = 0;
   e->prep_pending = false;
-  e->d_planes = nullptr;
   e->d_recs = nullptr;
   e->d_lo = nullptr;
   e->d_row_off = nullptr;
@@ -711,7 +716,7 @@ void build_shard(ldp_engine* e) {
       }
     }
   }
-  free_device(e);
+  free_device(e, e->replan_keeps_image);  // (a new plan: the device arrays of the old one go -- all of them, unless ldp_restrict_variants() is planning a loaded engine)
   e->mf_enabled = e->opt.pair_mfma && (!e->matrix_mode) && (!e->band_r2_mode) && (e->P.founder_ct <= kMfMaxFounders);
   e->mf_wgs.clear();
   e->wd_tiles.clear();
@@ -932,6 +937,8 @@ void build_shard(ldp_engine* e) {
   e->recs_host_valid = false;
   e->maj_freq.assign(local, 0.0);
   e->mf_set.assign(local, 0);
+  e->row_inv_loaded.assign(local, 0);
+  e->loaded_special = false;
 }
 
 // Device selection and stream creation, at the first use of the device: ldp_create() and ldp_set_variants() are host
@@ -995,12 +1002,13 @@ int ensure_device_plan(ldp_engine* e) {
   const size_t n = std::max<size_t>(e->local_ct, 1);
   e->codes_format = e->opt.pair_mfma && (e->P.founder_ct <= kMfMaxFounders);
   e->code_row_bytes = code_row_bytes_of(e->P.founder_ct);
-  if (e->codes_format) {
+  // (an engine that ldp_restrict_variants() has just planned again keeps its image, and the row flags that describe it)
+  if (e->codes_format && !e->d_codes) {
     HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_codes), n * e->code_row_bytes));
     HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_stored_inv), n));
     HIP_TRY(e, hipMemsetAsync(e->d_stored_inv, 0, n, e->stream));
     e->any_stored_inv = false;
-  } else {
+  } else if ((!e->codes_format) && !e->d_planes) {
     HIP_TRY(e, hipMalloc(&e->d_planes, n * e->row_dwords * sizeof(uint32_t)));
   }
   mark("image hipMalloc");
@@ -1051,7 +1059,12 @@ int ensure_device_plan(ldp_engine* e) {
   for (int k = 0; k < kCheckpoints; ++k) {
     e->checkpoint_chunk[k] = 0xffffffffu;
   }
-  if ((e->chunks >= 4) && !e->matrix_mode) {
+  if (e->cp_frozen) {
+    e->n_checkpoints = e->frozen_n_checkpoints;
+    for (int k = 0; k < kCheckpoints; ++k) {
+      e->checkpoint_chunk[k] = e->frozen_cp_chunk[k];
+    }
+  } else if ((e->chunks >= 4) && !e->matrix_mode) {
     double frac[kCheckpoints];
     const int nf = checkpoint_fractions(e->P.prune_last_param, frac);
     for (int k = 0; k < nf; ++k) {
@@ -1706,6 +1719,8 @@ int ldp_debug_set_option(ldp_engine* e, const char* name, double value) {
     e->opt.decode_no_lds = (value != 0.0);
   } else if (n == "x_rows") {
     e->opt.x_rows = static_cast<uint32_t>(std::max(0.0, value));
+  } else if (n == "compact_batch_rows") {
+    e->opt.compact_batch_rows = static_cast<uint32_t>(std::min(std::max(0.0, value), 4294967295.0));
   } else {
     return fail(e, LDP_ERR_INVALID, "unknown option: " + n);
   }

@@ -205,6 +205,7 @@ struct EngineOptions {
   uint32_t decode_rows = 0;    // "decode_rows" k: record decode in launches of k rows (LD chains cut everywhere)
   bool decode_no_lds = false;  // "decode_no_lds" 1: decoded rows are assembled in global memory (what rows beyond 128 KiB take) instead of LDS
   uint32_t x_rows = 0;         // "x_rows" k: the chrX-weighted blocks in chunks of k rows
+  uint32_t compact_batch_rows = 0;  // "compact_batch_rows" k: ldp_restrict_variants() moves the image in batches of k rows (0: as many as 256 MiB hold)
 };
 
 constexpr uint32_t kStageSlots = 4;  // pinned staging ring of host-memory input
@@ -292,6 +293,9 @@ struct ldp_engine {
   std::vector<double> maj_freq;           // local
   std::vector<uint8_t> mf_set;            // local: 0 unset, 1 caller-supplied, 2 to be derived from device counts, 3 derived
   std::vector<uint64_t> preferred;        // global bitmap (may be empty)
+  std::vector<uint8_t> row_inv_loaded;    // local: the row was loaded as LDP_GENO_INVERSE (the call's encoding, or a collapsed multiallelic record)
+  bool loaded_special = false;            // some row came as LDP_GENO_PHASED or through a sample map that is no plain subset: a count of the image row alone
+                                          // would not give its record again (ldp_restrict_variants refuses such engines)
 
   // ---- device ----
   // The resident genotype image: 2-bit codes for the matrix-pipe kernels (ldp_device.h; the default), hom / ref2het bit-planes
@@ -385,6 +389,15 @@ struct ldp_engine {
   uint64_t dec_next_offset = 0;        // ... and the file offset right behind that call's last record
 
   ldp_counters ctr;
+  // ldp_restrict_variants(): the last call's compaction (ldp_debug_get_compact_stats)
+  uint64_t rows_compacted = 0, rows_direct = 0, rows_bounced = 0;
+  double ms_compact = 0.0;
+  // a bit-plane engine that was restricted keeps the checkpoint statistics its rows were counted with -- and with them the checkpoints
+  // of the plan they were loaded under (none for ldp_set_variants_matrix) -- until its device memory is released
+  bool replan_keeps_image = false;  // set around the ldp_set_variants() of ldp_restrict_variants(): build_shard() frees the plan-sized device arrays only
+  bool cp_frozen = false;
+  uint32_t frozen_cp_chunk[kCheckpoints];
+  uint32_t frozen_n_checkpoints = 0;
 
   ldp_engine() { memset(&ctr, 0, sizeof(ctr)); }
 };
@@ -452,6 +465,9 @@ void plan_mfma_generic(const std::vector<std::pair<uint32_t, uint32_t>>& runs, c
                        std::vector<MfmaTile>* out_tiles = nullptr, uint32_t wide_min_reach = kWdMinReach);
 uint32_t partition_diag(std::vector<MfmaWG>* wgs, size_t first, size_t ct);
 void build_shard(ldp_engine* e);
+void subcontig_split(const uint32_t* chr_idx, const uint32_t* bps, uint32_t variant_ct, uint32_t window, std::vector<Subcontig>* subs, uint32_t* window_max_out);
+// everything the engine holds on the device; keep_image: all but the resident image with its row flags, the staging ring and the load paths' scratch
+void free_device(ldp_engine* e, bool keep_image = false);
 void bind_gpu(ldp_engine* e);
 int ensure_device_plan(ldp_engine* e);
 int ensure_staging(ldp_engine* e);
@@ -468,6 +484,14 @@ inline size_t tile_counts_pin_offset(const ldp_engine* e) { return 4 + ((e->grou
 hipError_t queue_route(ldp_engine* e, size_t slot, hipStream_t stream, int allow_sparse, uint32_t row_end);
 int launch_ready_groups(ldp_engine* e);
 }  // namespace ldph
+
+// ldp_engine_load.cpp (defined inside its extern "C" block)
+extern "C" {
+namespace ldph LDP_HIDDEN {
+int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void* geno, uint64_t stride_bytes, int location, int encoding, const uint8_t* d_row_inverse,
+                   const uint8_t* h_row_inverse, int src_fd, uint64_t src_off);
+}
+}
 
 using namespace ldph;
 #endif

@@ -10,7 +10,7 @@ namespace ldph LDP_HIDDEN {
 // src_fd >= 0: the rows are read from that file descriptor at src_off + (variant - first_variant) * stride_bytes (pread straight into
 // the pinned ring; `geno` is unused and location is LDP_MEM_HOST)
 int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void* geno, uint64_t stride_bytes, int location, int encoding,
-                   const uint8_t* d_row_inverse, const uint8_t* h_row_inverse, int src_fd = -1, uint64_t src_off = 0) {
+                   const uint8_t* d_row_inverse, const uint8_t* h_row_inverse, int src_fd, uint64_t src_off) {
   if (!e) {
     return LDP_ERR_INVALID;
   }
@@ -303,6 +303,15 @@ int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void
       }
       std::fill(e->loaded.begin() + l0, e->loaded.begin() + l0 + cnt, static_cast<uint8_t>(1));
       std::fill(e->load_tag.begin() + l0, e->load_tag.begin() + l0 + cnt, e->load_epoch);
+      // (what ldp_restrict_variants() needs to count the rows again where they lie)
+      if (!h_row_inverse) {
+        std::fill(e->row_inv_loaded.begin() + l0, e->row_inv_loaded.begin() + l0 + cnt, static_cast<uint8_t>(base_encoding == LDP_GENO_INVERSE));
+      } else {
+        for (uint32_t q = 0; q < cnt; ++q) {
+          e->row_inv_loaded[l0 + q] = ((base_encoding == LDP_GENO_INVERSE) || h_row_inverse[g + done + q - first_variant]) ? 1 : 0;
+        }
+      }
+      e->loaded_special = e->loaded_special || phased || (mapped && !e->map_is_subset);
       if (base_encoding != LDP_GENO_INVERSE) {
         // derived from the device's allele counts at the next ldp_run()
         if (!h_row_inverse) {
@@ -348,7 +357,7 @@ int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void
 }  // namespace ldph
 
 int ldp_load_genotypes(ldp_engine* e, uint32_t first_variant, uint32_t n, const void* geno, uint64_t stride_bytes, int location, int encoding) {
-  return load_rows_impl(e, first_variant, n, geno, stride_bytes, location, encoding, nullptr, nullptr);
+  return load_rows_impl(e, first_variant, n, geno, stride_bytes, location, encoding, nullptr, nullptr, -1, 0);
 }
 
 int ldp_load_genotypes_fd(ldp_engine* e, uint32_t first_variant, uint32_t n, int fd, uint64_t file_offset, uint64_t stride_bytes, int encoding) {
@@ -711,7 +720,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       }
     }
     status = load_rows_impl(e, first_variant + q0, cnt, DA.rows, lstride, LDP_MEM_DEVICE, LDP_GENO_REF | (mapped ? LDP_GENO_MAPPED : 0) | (phased ? LDP_GENO_PHASED : 0),
-                            multi.empty() ? nullptr : DA.row_inverse, multi.empty() ? nullptr : h_inverse.data());
+                            multi.empty() ? nullptr : DA.row_inverse, multi.empty() ? nullptr : h_inverse.data(), -1, 0);
     if (LDP_ENV("LDP_DEBUG_TIMELINE")) {
       fprintf(stderr, "decode launch of %u rows: queued in %.3f ms, device done %.3f ms later, rows loaded %.3f ms after that\n", rows, t_q - t_call, t_s - t_q, now_ms() - t_s);
     }

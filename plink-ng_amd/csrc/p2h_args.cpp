@@ -695,6 +695,8 @@ bool parse_misc_flags(Args& A, ArgCursor& c, const std::string& f) {
     g_dbg.alias_devices = true;   // (test hook: the N engines of --gpus N dealt onto the devices there are, host transport for the exchange)
   } else if (f == "--debug-x-host") {
     g_dbg.x_host = true;          // (test hook: chrX pairs as lists through ldp_pair_stats and the host arithmetic)
+  } else if (f == "--debug-host-filter") {
+    g_dbg.host_filter = true;     // (measurement / test hook: --geno / --maf / --mac from the host's pass over the rows, never from the device's records)
   } else if (f == "--debug-host-decode") {
     g_dbg.host_decode = true;     // (measurement / test hook: variable-width records decoded by the host reader)
   } else if (f == "--debug-no-bind") {

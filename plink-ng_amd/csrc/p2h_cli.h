@@ -235,6 +235,7 @@ enum : uint32_t {
 // test / measurement hooks of the front-end (hidden --debug-* flags; the library itself reads no environment, csrc/ldp_env.h)
 struct DebugHooks {
   bool alias_devices = false, x_host = false, host_decode = false, load_map = false, no_bind = false, serial_feed = false;
+  bool host_filter = false;  // --debug-host-filter: --geno / --maf / --mac always from the host's own pass over the rows
   uint32_t x_rows = 0, decode_threads = 0;
 };
 extern DebugHooks g_dbg;
@@ -529,6 +530,13 @@ struct Session {
   std::vector<uint32_t> mk, xk, yk, tk;  // indices into inc[]: main engine, chrX, chrY, MT under --indep-pairphase
   uint32_t m_ct = 0;
   std::vector<uint32_t> m_chr, m_bps;
+  // the count filters (CountFilters): given at all; left to run_prune(), which decides them from the engine's records after the load
+  // (then inc[] still holds every variant the table filters leave); otherwise why not, and what the host's pass took
+  bool count_filters = false, device_filter = false;
+  const char* host_filter_reason = nullptr;
+  double host_filter_s = 0.0;
+  uint32_t kept_sample_ct = 0;
+  std::vector<uint8_t> inc_chr0;  // device_filter: 1 = inc[k] lies on chromosome 0 (empty or shorter than inc: the rest is 0)
   // (... and, once the runtime is up, this thread -- the one that creates the engines, their copy threads and their pinned staging -- moves next to the device)
   void join_hip() {
     if (t_hip.joinable()) {
@@ -550,6 +558,27 @@ struct Session {
     }
   }
 };
+
+// --geno / --maf / --max-maf / --mac / --max-mac on one variant's genotype counts, as the reference enforces them (EnforceGenoThresh
+// plink2_filter.cc:3498, EnforceFreqConstraints :3791): the one arithmetic both sources of the counts go through -- the host's pass over
+// the rows (load_inputs) and the records of the engine's own count pass (run_prune: ldp_get_variant_recs, then ldp_restrict_variants).
+struct CountFilters {
+  const Args& A;
+  bool geno_on, mac_on, freq_on;
+  uint32_t missing_max;
+  double min_maf, max_maf;
+  uint32_t geno_removed = 0, freq_removed = 0;
+  CountFilters(const Args& args, uint32_t kept_samples);
+  bool any() const { return geno_on || freq_on; }
+  // true: the variant goes (and is counted under the filter that removed it).  missing: calls missing among the kept samples; ref2 / het /
+  // alt2: the founders' genotype counts; dosage: their (ref, alt) dosage sums in 16384ths of a copy when the record has a dosage track
+  bool drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t alt2, const std::pair<uint64_t, uint64_t>* dosage = nullptr);
+  void log_counts() const;  // the reference's two log lines
+};
+// Why a job's count filters cannot be decided from the device's records (nullptr: they can).  The image holds founder columns only and
+// --geno counts over the kept samples; one engine holds every row only with one GPU; the r^2 outputs, --clump and --indep-pairphase keep
+// the host's pass (their engines are planned before the load); dosage-based frequencies never reach the device.
+const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_samples, uint32_t founder_ct);
 
 void load_inputs(Session& S, int argc, char** argv);
 int run_r2(Session& S);

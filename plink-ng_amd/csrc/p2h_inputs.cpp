@@ -169,6 +169,76 @@ void count_rows(const uint8_t* rows, uint64_t stride, uint32_t n_rows, bool bed,
 }
 
 
+CountFilters::CountFilters(const Args& args, uint32_t kept_samples) : A(args) {
+  geno_on = (A.geno != 1.0);
+  mac_on = (A.min_allele_ddosage != 0) || (A.max_allele_ddosage != ~0ull);
+  freq_on = (A.min_maf != 0.0) || (A.max_maf != 1.0) || mac_on;
+  missing_max = static_cast<uint32_t>(static_cast<int32_t>(A.geno * (1 + kSmallEpsilon) * static_cast<double>(kept_samples)));
+  min_maf = A.min_maf * (1.0 - kSmallEpsilon);
+  max_maf = A.max_maf * (1.0 + kSmallEpsilon);
+}
+
+bool CountFilters::drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t alt2, const std::pair<uint64_t, uint64_t>* dosage) {
+  if (geno_on && (missing > missing_max)) {
+    ++geno_removed;
+    return true;
+  }
+  if (freq_on) {
+    // allele counts in 16384ths of a copy: the hardcalls', or -- a record with dosages -- the founders' dosage sums
+    uint64_t ref_ct = (2ull * ref2 + het) * 16384ull, alt_ct = (2ull * alt2 + het) * 16384ull;
+    if (dosage) {
+      ref_ct = dosage->first;
+      alt_ct = dosage->second;
+    }
+    const uint64_t tot = ref_ct + alt_ct;
+    if (mac_on) {
+      // GetTypedDdosage, nonmajor mode, two alleles (plink2_filter.cc:3765-3767) on allele_ddosages = 2 x these sums
+      // (plink2_data.cc:2441-2442)
+      const uint64_t typed_dd = 2 * std::min(ref_ct, alt_ct);
+      if ((typed_dd < A.min_allele_ddosage) || (typed_dd > A.max_allele_ddosage)) {
+        ++freq_removed;
+        return true;
+      }
+    }
+    const double ref_freq = tot ? (static_cast<double>(ref_ct) * (1.0 / static_cast<double>(tot))) : 0.5;  // plink2_filter.cc:2137-2147
+    const double nonref_freq = 1.0 - ref_freq;
+    const double typed = (nonref_freq < ref_freq) ? nonref_freq : ref_freq;  // GetTypedFreq, nonmajor mode, two alleles (:3715-3723)
+    if ((((A.min_maf != 0.0) || (A.max_maf != 1.0))) && (((A.min_maf != 0.0) && (typed < min_maf)) || ((A.max_maf < 1.0) && (typed > max_maf)))) {
+      ++freq_removed;
+      return true;
+    }
+  }
+  return false;
+}
+
+void CountFilters::log_counts() const {
+  if (geno_on) {
+    logprintf("--geno: %u variant%s removed due to missing genotype data.\n", geno_removed, (geno_removed == 1) ? "" : "s");
+  }
+  if (freq_on) {
+    logprintf("%u variant%s removed due to allele frequency threshold(s)\n(--maf/--max-maf/--mac/--max-mac).\n", freq_removed, (freq_removed == 1) ? "" : "s");
+  }
+}
+
+const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_samples, uint32_t founder_ct) {
+  if (g_dbg.host_filter) {
+    return "--debug-host-filter";
+  }
+  if ((!A.have_prune) || A.pairphase) {
+    return A.pairphase ? "--indep-pairphase plans its engines before the load" : "the r^2 outputs and --clump plan their engines before the load";
+  }
+  if (A.gpus != 1) {
+    return "more than one GPU (no engine holds every row)";
+  }
+  if (has_dosage) {
+    return "the file has dosage tracks (frequencies come from the dosages)";
+  }
+  if (kept_samples != founder_ct) {
+    return "non-founders among the kept samples (--geno counts them, the device's rows hold founders only)";
+  }
+  return nullptr;
+}
+
 void load_inputs(Session& S, int argc, char** argv) {
   S.t_begin = now_s();
   S.A = parse_args(argc, argv);
@@ -388,108 +458,91 @@ void load_inputs(Session& S, int argc, char** argv) {
         m_f[sx >> 5] |= 1ull << (2 * (sx & 31));
       }
     }
-    std::vector<RowCounts> counts(todo.size());
-    const bool bed = (S.storage_mode == 0x01);
-    const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-    if (S.direct_rows) {
-      std::atomic<size_t> next(0);
-      const size_t kTask = 2048;
-      std::vector<std::thread> pool;
-      for (uint32_t t = 0; t < nthreads; ++t) {
-        pool.emplace_back([&]() {
-          for (size_t q0 = next.fetch_add(kTask); q0 < todo.size(); q0 = next.fetch_add(kTask)) {
-            const size_t q1 = std::min(todo.size(), q0 + kTask);
-            for (size_t q = q0; q < q1; ++q) {
-              count_rows(S.direct_rows + static_cast<uint64_t>(todo[q]) * S.rec_bytes, S.rec_bytes, 1, bed, raw_sample_ct, m_f, m_s, &counts[q]);
-            }
-          }
-        });
-      }
-      for (std::thread& th : pool) {
-        th.join();
-      }
-    } else {
-      // variable-width records: decode runs of file-consecutive variants (all host threads), then count them
-      const uint32_t max_run = std::max<uint32_t>(1, static_cast<uint32_t>((256ull << 20) / std::max<uint64_t>(S.rec_bytes, 1)));
-      std::vector<uint8_t> decoded;
-      for (size_t q0 = 0; q0 < todo.size();) {
-        uint32_t run = 1;
-        while ((q0 + run < todo.size()) && (todo[q0 + run] == todo[q0] + run) && (run < max_run)) {
-          ++run;
-        }
-        decoded.resize(static_cast<size_t>(run) * S.rec_bytes);
-        if (ldp_pgen_read(pg, todo[q0], run, decoded.data(), S.rec_bytes, 0)) {
-          die(6, "Error: %s: %s\n", gpath.c_str(), ldp_pgen_last_error(pg));
-        }
-        std::atomic<uint32_t> next(0);
+    // The engine's count pass makes the same counts a moment later, on the device: where the job allows it the variants are loaded
+    // first and the filters decided from its records (run_prune: ldp_get_variant_recs + ldp_restrict_variants), and this pass is skipped.
+    // (--dry-run plans on the final variant list without a device: it takes the pass and says which one a run would take.)
+    S.count_filters = true;
+    S.kept_sample_ct = kept_samples;
+    S.host_filter_reason = device_filter_refusal(A, S.has_dosage, kept_samples, founder_ct);
+    if (A.dry_run) {
+      logprintf("dry-run: variant filters: %s%s\n", S.host_filter_reason ? "host pass: " : "from the device's count pass", S.host_filter_reason ? S.host_filter_reason : "");
+    }
+    S.device_filter = (!S.host_filter_reason) && !A.dry_run;
+    const double t_filter0 = now_s();
+    if (!S.device_filter) {
+      std::vector<RowCounts> counts(todo.size());
+      const bool bed = (S.storage_mode == 0x01);
+      const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+      if (S.direct_rows) {
+        std::atomic<size_t> next(0);
+        const size_t kTask = 2048;
         std::vector<std::thread> pool;
         for (uint32_t t = 0; t < nthreads; ++t) {
           pool.emplace_back([&]() {
-            for (uint32_t r0 = next.fetch_add(256); r0 < run; r0 = next.fetch_add(256)) {
-              const uint32_t n = std::min(256u, run - r0);
-              count_rows(decoded.data() + static_cast<uint64_t>(r0) * S.rec_bytes, S.rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &counts[q0 + r0]);
+            for (size_t q0 = next.fetch_add(kTask); q0 < todo.size(); q0 = next.fetch_add(kTask)) {
+              const size_t q1 = std::min(todo.size(), q0 + kTask);
+              for (size_t q = q0; q < q1; ++q) {
+                count_rows(S.direct_rows + static_cast<uint64_t>(todo[q]) * S.rec_bytes, S.rec_bytes, 1, bed, raw_sample_ct, m_f, m_s, &counts[q]);
+              }
             }
           });
         }
         for (std::thread& th : pool) {
           th.join();
         }
-        q0 += run;
-      }
-    }
-    if (S.has_dosage && freq_filter) {
-      std::vector<uint32_t> with_track;
-      for (uint32_t v : todo) {
-        if (ldp_pgen_variant_has_dosage(pg, v)) {
-          with_track.push_back(v);
+      } else {
+        // variable-width records: decode runs of file-consecutive variants (all host threads), then count them
+        const uint32_t max_run = std::max<uint32_t>(1, static_cast<uint32_t>((256ull << 20) / std::max<uint64_t>(S.rec_bytes, 1)));
+        std::vector<uint8_t> decoded;
+        for (size_t q0 = 0; q0 < todo.size();) {
+          uint32_t run = 1;
+          while ((q0 + run < todo.size()) && (todo[q0 + run] == todo[q0] + run) && (run < max_run)) {
+            ++run;
+          }
+          decoded.resize(static_cast<size_t>(run) * S.rec_bytes);
+          if (ldp_pgen_read(pg, todo[q0], run, decoded.data(), S.rec_bytes, 0)) {
+            die(6, "Error: %s: %s\n", gpath.c_str(), ldp_pgen_last_error(pg));
+          }
+          std::atomic<uint32_t> next(0);
+          std::vector<std::thread> pool;
+          for (uint32_t t = 0; t < nthreads; ++t) {
+            pool.emplace_back([&]() {
+              for (uint32_t r0 = next.fetch_add(256); r0 < run; r0 = next.fetch_add(256)) {
+                const uint32_t n = std::min(256u, run - r0);
+                count_rows(decoded.data() + static_cast<uint64_t>(r0) * S.rec_bytes, S.rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &counts[q0 + r0]);
+              }
+            });
+          }
+          for (std::thread& th : pool) {
+            th.join();
+          }
+          q0 += run;
         }
       }
-      S.need_dosage_sums(with_track);
-    }
-    drop_by_counts.assign(raw_variant_ct, 0);
-    uint32_t geno_removed = 0, freq_removed = 0;
-    const uint32_t missing_max = static_cast<uint32_t>(static_cast<int32_t>(A.geno * (1 + kSmallEpsilon) * static_cast<double>(kept_samples)));
-    const double min_maf = A.min_maf * (1.0 - kSmallEpsilon), max_maf = A.max_maf * (1.0 + kSmallEpsilon);
-    for (size_t q = 0; q < todo.size(); ++q) {
-      const RowCounts& c = counts[q];
-      if ((A.geno != 1.0) && (c.missing > missing_max)) {
-        drop_by_counts[todo[q]] = 1;
-        ++geno_removed;
-        continue;
-      }
-      if (freq_filter) {
-        // allele counts in 16384ths of a copy: the hardcalls', or -- a record with dosages -- the founders' dosage sums
-        uint64_t ref_ct = (2ull * c.ref2 + c.het) * 16384ull, alt_ct = (2ull * c.alt2 + c.het) * 16384ull;
-        const auto dd = S.dosage_sums.find(todo[q]);
-        if (dd != S.dosage_sums.end()) {
-          ref_ct = dd->second.first;
-          alt_ct = dd->second.second;
-        }
-        const uint64_t tot = ref_ct + alt_ct;
-        if (mac_filter) {
-          // GetTypedDdosage, nonmajor mode, two alleles (plink2_filter.cc:3765-3767) on allele_ddosages = 2 x these sums
-          // (plink2_data.cc:2441-2442)
-          const uint64_t typed_dd = 2 * std::min(ref_ct, alt_ct);
-          if ((typed_dd < A.min_allele_ddosage) || (typed_dd > A.max_allele_ddosage)) {
-            drop_by_counts[todo[q]] = 1;
-            ++freq_removed;
-            continue;
+      if (S.has_dosage && freq_filter) {
+        std::vector<uint32_t> with_track;
+        for (uint32_t v : todo) {
+          if (ldp_pgen_variant_has_dosage(pg, v)) {
+            with_track.push_back(v);
           }
         }
-        const double ref_freq = tot ? (static_cast<double>(ref_ct) * (1.0 / static_cast<double>(tot))) : 0.5;  // plink2_filter.cc:2137-2147
-        const double nonref_freq = 1.0 - ref_freq;
-        const double typed = (nonref_freq < ref_freq) ? nonref_freq : ref_freq;  // GetTypedFreq, nonmajor mode, two alleles (:3715-3723)
-        if ((((A.min_maf != 0.0) || (A.max_maf != 1.0))) && (((A.min_maf != 0.0) && (typed < min_maf)) || ((A.max_maf < 1.0) && (typed > max_maf)))) {
+        S.need_dosage_sums(with_track);
+      }
+      drop_by_counts.assign(raw_variant_ct, 0);
+      CountFilters F(A, kept_samples);
+      for (size_t q = 0; q < todo.size(); ++q) {
+        const RowCounts& c = counts[q];
+        // (a record with dosages: the founders' dosage sums instead of the hardcalls' allele counts)
+        const auto dd = S.dosage_sums.find(todo[q]);
+        if (F.drops(c.missing, c.ref2, c.het, c.alt2, (dd != S.dosage_sums.end()) ? &dd->second : nullptr)) {
           drop_by_counts[todo[q]] = 1;
-          ++freq_removed;
         }
       }
-    }
-    if (A.geno != 1.0) {
-      logprintf("--geno: %u variant%s removed due to missing genotype data.\n", geno_removed, (geno_removed == 1) ? "" : "s");
-    }
-    if (freq_filter) {
-      logprintf("%u variant%s removed due to allele frequency threshold(s)\n(--maf/--max-maf/--mac/--max-mac).\n", freq_removed, (freq_removed == 1) ? "" : "s");
+      F.log_counts();
+      S.host_filter_s = now_s() - t_filter0;
+      if (A.timing) {
+        logprintf("[timing] variant filters: host pass (%.3f s; %s)\n", S.host_filter_s, S.host_filter_reason ? S.host_filter_reason : "--dry-run");
+      }
     }
   }
   {
@@ -536,8 +589,14 @@ void load_inputs(Session& S, int argc, char** argv) {
         continue;
       }
       if (zero && (A.have_prune || (A.r2_table && !A.r2_inter))) {  // (the all-pairs modes keep chromosome 0)
-        ++skipped;
-        continue;
+        if (!S.device_filter) {
+          ++skipped;
+          continue;
+        }
+        // (the count filters see chromosome 0 too, and only what they leave of it is "ignored": such variants are loaded and filtered with
+        // the others, and run_prune() drops and reports the survivors)
+        S.inc_chr0.resize(inc.size() + 1, 0);
+        S.inc_chr0.back() = 1;
       }
       if (cls == 2) {
         die(6, "Error: Invalid chromosome code '%s'. (Use --allow-extra-chr to force it to be accepted.)\n", cur.c_str());
@@ -582,7 +641,7 @@ void load_inputs(Session& S, int argc, char** argv) {
       die(7, "Error: All %u variant%s in %s excluded by %s.\n", raw_variant_ct, (raw_variant_ct == 1) ? "" : "s", (A.pvar.empty() ? A.bim : A.pvar).c_str(), flags.c_str());
     }
   }
-  const bool any_main_filter = chr_filter || (!A.extract_files.empty()) || (!A.exclude_files.empty()) || (!drop_by_counts.empty()) || (A.max_alleles != 0xffffffffu) || A.snps_only;
+  const bool any_main_filter = chr_filter || (!A.extract_files.empty()) || (!A.exclude_files.empty()) || (!drop_by_counts.empty()) || S.device_filter || (A.max_alleles != 0xffffffffu) || A.snps_only;
   if (any_main_filter && inc.empty() && (!skipped)) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
     die(13, "Error: No variants remaining after main filters.\n");
   }
@@ -591,7 +650,7 @@ void load_inputs(Session& S, int argc, char** argv) {
   }
   S.variant_ct = static_cast<uint32_t>(inc.size());
   const uint32_t variant_ct = S.variant_ct;
-  if (A.window_is_bp || A.r2_table) {
+  if ((A.window_is_bp || A.r2_table) && !S.device_filter) {  // (device_filter: the check is about the variants the count filters leave, run_prune())
     for (uint32_t k = 1; k < variant_ct; ++k) {
       if (chr_idx[k] == chr_idx[k - 1] && bps[k] < bps[k - 1]) {
         if (A.have_prune) {  // plink2.cc:2926-2929

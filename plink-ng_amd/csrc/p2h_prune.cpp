@@ -68,13 +68,16 @@ struct PruneJob {
   const uint8_t* const direct_rows = S.direct_rows;
   const std::vector<uint32_t>&inc = S.inc, &chr_idx = S.chr_idx, &bps = S.bps;
   const std::vector<uint8_t>& vcls = S.vcls;
-  const uint32_t variant_ct = S.variant_ct, m_ct = S.m_ct;
+  uint32_t variant_ct = S.variant_ct, m_ct = S.m_ct;  // (filter_on_device() shrinks them together with the session's variant tables)
   const std::vector<uint32_t>&mk = S.mk, &xk = S.xk, &yk = S.yk, &tk = S.tk, &m_chr = S.m_chr, &m_bps = S.m_bps;
   const double &t_hip_init = S.t_hip_init, &t_parse = S.t_parse, &t_joined = S.t_joined;
 
   ldp_params P;
   bool duplicate_ids = false;
   double t_tables_done = 0, t_planned = 0, t_load0 = 0, t_load1 = 0, t_run1 = 0;
+  // the count filters decided from the engine's records (Session::device_filter)
+  uint64_t filter_rows_compacted = 0, filter_rows_bounced = 0;
+  double filter_ms_compact = 0.0, filter_s = 0.0, filter_ms_recount = 0.0;
   int world = 1, n_devices = 1;
   bool alias_devices = false;
   std::vector<ldp_engine*> eng;
@@ -208,7 +211,8 @@ struct PruneJob {
       if (rc) {
         die(16, "Error: ldp_create failed (%d).\n", rc);
       }
-      rc = ldp_set_variants(eng[r], m_ct, m_chr.data(), A.window_is_bp ? m_bps.data() : nullptr);
+      // (count filters from the device's records: rows, count pass and records first, no band -- filter_on_device() plans)
+      rc = S.device_filter ? ldp_set_variants_matrix(eng[r], m_ct) : ldp_set_variants(eng[r], m_ct, m_chr.data(), A.window_is_bp ? m_bps.data() : nullptr);
       if (rc) {
         die(16, "Error: %s\n", ldp_last_error(eng[r]));
       }
@@ -721,6 +725,93 @@ struct PruneJob {
     }
   }
 
+  // --geno / --maf / --max-maf / --mac / --max-mac from the records the load's own count pass left on the device (nm_ct and the three
+  // genotype counts of every row, over the founders = the kept samples: device_filter_refusal): the arithmetic of the host's pass
+  // (CountFilters), then the engine drops the variants that go and plans over the rest (ldp_restrict_variants), and the session's variant
+  // tables follow.  One engine, autosomes only, no multiallelic variant: mk is every variant.
+  void filter_on_device() {
+    const double t0 = now_s();
+    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
+    if (ldp_get_variant_recs(eng[0], 0, m_ct, recs.data())) {
+      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+    }
+    CountFilters F(A, S.kept_sample_ct);
+    std::vector<uint64_t> keep((static_cast<size_t>(m_ct) + 63) / 64 + 1, 0);
+    uint32_t kept = 0, chr0_left = 0;
+    for (uint32_t q = 0; q < m_ct; ++q) {
+      const ldp_variant_rec& r = recs[q];
+      if (!F.drops(founder_ct - r.nm_ct, r.n_homref, r.n_het, r.n_homalt)) {
+        if ((q < S.inc_chr0.size()) && S.inc_chr0[q]) {
+          ++chr0_left;  // (never pruned, never listed: LdPrune strips chromosome 0, plink2_ld.cc:2542)
+          continue;
+        }
+        keep[q >> 6] |= 1ull << (q & 63);
+        // (mk[q] == q here: the tables are compacted in place)
+        S.inc[kept] = S.inc[q];
+        S.chr_idx[kept] = S.chr_idx[q];
+        S.bps[kept] = S.bps[q];
+        S.vcls[kept] = S.vcls[q];
+        ++kept;
+      }
+    }
+    F.log_counts();
+    if ((!kept) && !chr0_left) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
+      filter_s = now_s() - t0;
+      report_filter_timing();
+      die(13, "Error: No variants remaining after main filters.\n");
+    }
+    if (chr0_left) {
+      logprintf("--indep-pairwise: Ignoring %u chromosome 0 variant%s.\n", chr0_left, chr0_left == 1 ? "" : "s");
+    }
+    S.inc_chr0.clear();
+    S.inc.resize(kept);
+    S.chr_idx.resize(kept);
+    S.bps.resize(kept);
+    S.vcls.resize(kept);
+    S.mk.resize(kept);
+    S.m_chr = S.chr_idx;
+    S.m_bps = S.bps;
+    S.variant_ct = S.m_ct = variant_ct = m_ct = kept;
+    for (uint32_t k = 1; A.window_is_bp && (k < kept); ++k) {
+      if ((chr_idx[k] == chr_idx[k - 1]) && (bps[k] < bps[k - 1])) {  // plink2.cc:2926-2929
+        die(6, "Error: When the window size is in kb units, LD-based pruning requires a sorted\n.pvar/.bim.  Retry this command after using --make-pgen/--make-bed +\n--sort-vars to sort your data.\n");
+      }
+    }
+    if (ldp_restrict_variants(eng[0], keep.data(), kept, m_chr.data(), A.window_is_bp ? m_bps.data() : nullptr)) {
+      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+    }
+    ldp_get_subcontigs(eng[0], &subcontig_ct, nullptr, 0);
+    (void)ldp_debug_get_compact_stats(eng[0], &filter_rows_compacted, nullptr, &filter_rows_bounced, &filter_ms_compact);
+    removed.assign((static_cast<size_t>(variant_ct) + 63) / 64 + 1, 0);
+    if (A.timing && kept) {
+      // (the count pass that ran over the kept rows in place: fetching the records -- the run wants them anyway -- closes its event pair)
+      ldp_variant_rec first;
+      ldp_counters c;
+      if ((ldp_get_variant_recs(eng[0], 0, 1, &first) == LDP_OK) && (ldp_get_counters(eng[0], &c) == LDP_OK)) {
+        filter_ms_recount = c.ms_prepare;
+      }
+    }
+    filter_s = now_s() - t0;
+  }
+
+  void report_filter_timing() {
+    if (!A.timing) {
+      return;
+    }
+    logprintf("[timing] variant filters: from the device's count pass (%llu rows compacted, %.3f ms; records, filter arithmetic and the new plan %.3f s in all)\n",
+              static_cast<unsigned long long>(filter_rows_compacted), filter_ms_compact, filter_s);
+    if ((founder_ct <= ldp_matrix_pipe_max_founders()) && (filter_ms_compact > 0.0) && (filter_ms_recount > 0.0)) {
+      // image rows of ceil(founders / 512) x 128 bytes: the compaction reads and writes a moved row once, twice when its batch goes through the bounce
+      // buffer (few rows dropped in front of it); the count pass reads the kept rows
+      const double pitch = static_cast<double>((static_cast<uint64_t>(founder_ct) + 511) / 512 * 128);
+      const double moved_gb = static_cast<double>(filter_rows_compacted) * pitch / 1e9, kept_gb = static_cast<double>(m_ct) * pitch / 1e9;
+      const double traffic_gb = 2.0 * static_cast<double>(filter_rows_compacted + filter_rows_bounced) * pitch / 1e9;
+      logprintf("[timing] compaction: %.3f GB of rows moved, %llu of %llu rows through the bounce buffer: %.3f GB of HBM traffic in %.3f ms = %.0f GB/s; the count pass over the kept rows in place: %.3f GB read in %.3f ms = %.0f GB/s\n",
+                moved_gb, static_cast<unsigned long long>(filter_rows_bounced), static_cast<unsigned long long>(filter_rows_compacted), traffic_gb, filter_ms_compact,
+                traffic_gb / (filter_ms_compact * 1e-3), kept_gb, filter_ms_recount, kept_gb / (filter_ms_recount * 1e-3));
+    }
+  }
+
   // every engine prunes its shard; several engines: their removed-bit segments meet (stitch, plink2_ld.cc:1418-1426)
   void run_diploid_engines() {
     t_load1 = now_s();
@@ -1056,7 +1147,9 @@ struct PruneJob {
     if (A.dry_run) {
       return dry_run();
     }
-    check_unique_ids();
+    if (!S.device_filter) {
+      check_unique_ids();
+    }
     t_tables_done = now_s();
     plan_engines();
     t_planned = now_s();
@@ -1065,21 +1158,38 @@ struct PruneJob {
       die(16, "Error: no usable HIP device (plink2-hip has no CPU compute path).\n");
     }
     removed.assign((static_cast<size_t>(variant_ct) + 63) / 64 + 1, 0);
+    if (S.device_filter) {
+      // load first, then filter and plan; the ID check and --indep-preferred are about the variants the filters leave
+      t_load0 = now_s();
+      set_row_geometry();
+      load_diploid_rows();
+      filter_on_device();
+      check_unique_ids();
+    }
     if (subcontig_ct || !xk.empty() || !yk.empty() || !tk.empty()) {
       check_before_loading();
       read_preferred();
       logprintf("--indep-pair%s (%d GPU%s): ", A.pairphase ? "phase" : "wise", world, world == 1 ? "" : "s");
       fflush(stdout);
-      t_load0 = now_s();
+      if (!S.device_filter) {
+        t_load0 = now_s();
+      }
       if (A.timing) {
         logprintf("\n[timing] table parse %.3f s, variant-table passes + ID check done at %.3f s, engine planned at %.3f s, HIP init %.3f s (concurrent; joined at %.3f s)\n",
                   t_parse, t_tables_done - t_begin, t_planned - t_begin, t_hip_init, t_joined - t_begin);
+        if (S.device_filter) {
+          report_filter_timing();  // (the host pass reports itself where it runs: load_inputs)
+        }
       }
-      set_row_geometry();
+      if (!S.device_filter) {
+        set_row_geometry();
+      }
       t_load1 = now_s();
       t_run1 = 0;
       if (subcontig_ct) {
-        load_diploid_rows();
+        if (!S.device_filter) {
+          load_diploid_rows();
+        }
         patch_host_built_rows();
         set_dosage_frequencies();
         S.file_to_hbm_done();  // (this thread moved next to device 0 for the file -> HBM leg, Session::join_hip: back to where it was)
