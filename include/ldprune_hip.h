@@ -422,6 +422,55 @@ int ldp_r2_unphased_band_rows(ldp_engine* e, uint32_t row_first, uint32_t row_ct
  * compares |r| with min_r2, so pass sqrt(threshold).  NaN where r^2 is undefined, as before. */
 int ldp_set_r_signed(ldp_engine* e, int mode);
 
+/* ---- --r2-phased / --r-phased (haplotype-frequency r^2, D, D'; PhasedLD plink2_ld.cc:4623-4765) ---- */
+/* What the statistic needs of a pair (ComputeR2NondosagePhasedStats, plink2_ld.cc:6545-6588), 0 = first (lower index) variant, 1 =
+ * second, all over the jointly called samples: their number, the two sums of the COUNTED allele (sum0, sum1: the reference's
+ * nmajsums), the haplotypes known to carry both counted alleles, and the samples heterozygous at both variants whose phase is not
+ * known.  WHICH allele is counted is not the caller's choice; it follows the reference, and it depends on `phase` below:
+ *   phase == NULL   the NON-major allele of each variant (what PgrGetInv1 hands the reference's LD code),
+ *   phase != NULL   the MAJOR allele (what PgrGetInv1P hands it for every variant of a file that has a hardcall-phase track:
+ *                   pgenlib_read.cc:7016-7042 inverts where PgrGetInv1 does not).
+ * r^2, D and D' are the same numbers on paper either way (D and r change sign together with one variant's orientation only), but not
+ * in the last bit, and the table prints the reference's doubles.  ldp_phased_ld() takes the tuple as it is: it never needs to know. */
+typedef struct {
+  uint32_t valid_obs;
+  uint32_t sum0;
+  uint32_t sum1;
+  uint32_t known_dotprod;
+  uint32_t unknown_hethet;
+} ldp_phased_stats_t;
+/* The five integers of the pairs i < j of a dense block (all-pairs plan; layout of ldp_pair_stats_block(): out[(second - row_first) *
+ * ld_elems + (first - col_first)], zero elsewhere) and of the band (windowed plan; layout of ldp_r2_unphased_band_rows()).  Exact
+ * integers from the matrix pipe: the six sums of ldp_pair_stats_t plus one more 0/1 product, the samples heterozygous at both
+ * variants (ldp_pair_phased.hip).  LDP_ERR_UNSUPPORTED on engines with more founders than ldp_matrix_pipe_max_founders() or with the
+ * matrix pipe switched off, and on sharded engines.
+ * phase: NULL (no phase information: .bed, .pgen without a hardcall-phase track), or a second engine on the same device with the same
+ * founder count and the same plan whose rows, loaded with LDP_GENO_REF, code every sample's PHASE at that variant:
+ *   00 = heterozygous and phased, the file's phaseinfo bit 0        10 = heterozygous and phased, phaseinfo bit 1
+ *   01 = anything else (not heterozygous, or no phase)              never 11
+ * The same kernels on those rows give what HardcallPhasedR2Refine (plink2_ld.cc:3238-3262) adds: double heterozygotes phased at both
+ * variants leave unknown_hethet, and those with equal orientation join known_dotprod.
+ * The six integers come from the engines' ordinary pair launches, one per row chunk: like ldp_pair_stats_block(), every ldp_r2_phased_*
+ * call therefore overwrites the launch fields of both engines' ldp_counters (candidate_pairs, computed_pairs, ms_pair_*,
+ * ms_run_total, the route / tile words) with those of its LAST chunk; ldp_debug_get_phased_filter() has the call's totals. */
+int ldp_r2_phased_stats_block(ldp_engine* e, ldp_engine* phase, uint32_t row_first, uint32_t row_ct, uint32_t col_first, uint32_t col_ct,
+                              ldp_phased_stats_t* out, uint64_t ld_elems);
+int ldp_r2_phased_band_stats(ldp_engine* e, ldp_engine* phase, uint32_t row_first, uint32_t row_ct, ldp_phased_stats_t* out, uint64_t capacity);
+/* The band's pairs that CAN reach min_r2, filtered on the device: every root the reference accepts lies in [0, K] (K = the unknown
+ * double heterozygotes' share), so D lies in [f11 - p q, f11 + K - p q] and r^2 <= max(|lo|, |hi|)^2 / (p q (1 - p)(1 - q)); |lo| and
+ * |hi| get an absolute slack of 2^-30 (the reference clips roots within 2^-32 of the interval and reports deviations of 7.9e-11,
+ * plink2_ld.cc:4664).  A pair whose bound is below min_r2 is dropped; monomorphic pairs, pairs without a joint sample and NaN bounds
+ * are kept.  unsquared != 0: min_r2 is a threshold on |r| (--r-phased; compared with the square root of the bound).  The caller runs
+ * ldp_phased_ld() on the survivors and applies the exact test: the filter only decides which pairs reach the host.
+ * out_stats / out_first / out_second (global variant indices, first < second) hold `capacity` entries, NO particular order; *count
+ * receives the number of survivors, and when it exceeds capacity only the first `capacity` stored are valid. */
+int ldp_r2_phased_band_hits(ldp_engine* e, ldp_engine* phase, uint32_t row_first, uint32_t row_ct, double min_r2, int unsquared,
+                            ldp_phased_stats_t* out_stats, uint32_t* out_first, uint32_t* out_second, uint64_t capacity, uint64_t* count);
+/* r^2, D, D' and the sign of D of n pairs from their integers, on HOST threads (no GPU involved; the arithmetic of PhasedLD,
+ * CubicRealRoots and EmPhaseUnscaledLnlike on the host's libm, so that the doubles are the reference's).  d, dprime, is_neg may be
+ * NULL.  Undefined pairs -- no joint sample, a variant monomorphic over the joint samples -- come back as NaN. */
+int ldp_phased_ld(const ldp_phased_stats_t* in, uint64_t n, double* r2, double* d, double* dprime, uint8_t* is_neg);
+
 /* ---- inspection ---- */
 int ldp_get_variant_recs(ldp_engine* e, uint32_t first_variant, uint32_t n, ldp_variant_rec* out);
 int ldp_get_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, double* out);

@@ -106,6 +106,12 @@ int ldp_debug_tile_classes(ldp_engine* e, uint8_t* out, uint64_t capacity, uint3
  * pointer may be NULL. */
 int ldp_debug_get_compact_stats(const ldp_engine* e, uint64_t* rows_compacted, uint64_t* rows_direct, uint64_t* rows_bounced, double* ms_compact);
 
+/* What the last ldp_r2_phased_* call on this engine did (ldp_counters has no room left for it): the pairs its device-side filter saw
+ * and the pairs it dropped (both 0 for the calls that do not filter), and the device time, HIP events on the engine's stream, of the
+ * double-heterozygote product kernel (ldp_pair_phased.hip) and of the six-integer pair launches of the same call, summed over its
+ * chunks and over both engines when there are phase rows.  Any pointer may be NULL. */
+int ldp_debug_get_phased_filter(const ldp_engine* e, uint64_t* pairs_seen, uint64_t* pairs_dropped, double* ms_hethet, double* ms_tuples);
+
 /* ---- synthetic workload (benchmark / test support, not part of the reference seam) ---- */
 /* Deterministic genotype generator for the SURVEY.md 8(d) workload: rows [first_variant, +n_variants) of
  * REF-based codes (LDP_GENO_REF) written to `out` (host or device memory), each genotype a pure function of

@@ -95,6 +95,7 @@ class ldp_tile_routes(ctypes.Structure):
 
 PAIR_STATS_DTYPE = np.dtype([("nm", "<u4"), ("sum1", "<i4"), ("ssq1", "<u4"), ("sum2", "<i4"), ("ssq2", "<u4"), ("dot", "<i4")])
 R2_HIT_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4"), ("r2", "<f8")])
+PHASED_STATS_DTYPE = np.dtype([("valid_obs", "<u4"), ("sum0", "<u4"), ("sum1", "<u4"), ("known_dotprod", "<u4"), ("unknown_hethet", "<u4")])
 VARIANT_REC_DTYPE = np.dtype([("nm_ct", "<u4"), ("sum", "<i4"), ("ssq", "<u4"), ("flags", "<u4"), ("n_homref", "<u4"),
                               ("n_het", "<u4"), ("n_homalt", "<u4"), ("reserved", "<u4")])
 
@@ -111,12 +112,14 @@ CABI_SYMBOLS = [
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats",
+    "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
 ]
 
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ("ldp_kernels.hip", "ldp_codes.hip", "ldp_pair_mfma.hip", "ldp_pair_wide.hip", "ldp_pred_csr.hip", "ldp_pgen_decode.hip", "ldp_synth.hip", "ldp_engine.cpp", "ldp_engine_run.cpp", "ldp_engine_r2.cpp",
-                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_pgen.cpp", "ldp_topology.cpp")]
+                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_pgen.cpp", "ldp_topology.cpp",
+                                          "ldp_pair_phased.hip", "ldp_engine_phased.cpp", "ldp_phased_ld.cpp")]
 
 
 def _stale(target, deps):
@@ -168,14 +171,14 @@ def build_library(force=False, verbose=False, measure=False):
 def cli_sources():
     """the front-end's translation units: main() + one unit per concern (csrc/p2h_cli.h is what they share)"""
     return [os.path.join(CSRC, f) for f in ("plink2_hip_cli.cpp", "p2h_util.cpp", "p2h_args.cpp", "p2h_tables.cpp", "p2h_inputs.cpp", "p2h_clump.cpp", "p2h_r2.cpp",
-                                            "p2h_prune.cpp")]
+                                            "p2h_r2_phased.cpp", "p2h_prune.cpp")]
 
 
 def build_cli(force=False, verbose=False):
     srcs = cli_sources()
     if not os.path.exists(srcs[0]):
         return None
-    deps = srcs + [LIB_PATH, os.path.join(CSRC, "p2h_cli.h"), os.path.join(REPO, "include", "ldprune_hip.h"), os.path.join(REPO, "include", "ldprune_hip_debug.h")]
+    deps = srcs + [LIB_PATH, os.path.join(CSRC, "p2h_cli.h"), os.path.join(CSRC, "p2h_r2_job.h"), os.path.join(REPO, "include", "ldprune_hip.h"), os.path.join(REPO, "include", "ldprune_hip_debug.h")]
     if force or _stale(CLI_PATH, deps):
         os.makedirs(BIN_DIR, exist_ok=True)
         cmd = ["hipcc", "-O2", "-std=c++17", "-ffp-contract=off", "-o", CLI_PATH] + srcs + ["-L" + LIB_DIR, "-lldprune_hip",
@@ -276,6 +279,11 @@ def lib():
     L.ldp_set_variants_vcor.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                         ctypes.c_uint32, ctypes.c_uint32]
     L.ldp_r2_unphased_band_rows.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_uint64]
+    L.ldp_r2_phased_stats_block.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
+    L.ldp_r2_phased_band_stats.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
+    L.ldp_r2_phased_band_hits.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_int, vp, u32p, u32p, ctypes.c_uint64, u64p]
+    L.ldp_phased_ld.argtypes = [vp, ctypes.c_uint64, f64p, f64p, f64p, u8p]
+    L.ldp_debug_get_phased_filter.argtypes = [vp, u64p, u64p, f64p, f64p]
     L.ldp_pgen_open.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.ldp_pgen_info.argtypes = [vp, u32p, u32p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.ldp_pgen_direct_rows.argtypes = [vp, u64p]
@@ -334,6 +342,20 @@ def matrix_pipe_max_founders():
 
 def device_count():
     return int(lib().ldp_device_count())
+
+
+def phased_ld(stats):
+    """ldp_phased_ld: r^2, D, D' and the sign of D of every entry of a PHASED_STATS_DTYPE array, on host threads (no GPU); NaN where the
+    statistic is undefined.  Returns (r2, d, dprime, is_neg) shaped like `stats`."""
+    st = np.ascontiguousarray(stats, dtype=PHASED_STATS_DTYPE)
+    n = st.size
+    r2, d, dp = (np.zeros(max(n, 1), dtype=np.float64) for _ in range(3))
+    neg = np.zeros(max(n, 1), dtype=np.uint8)
+    rc = lib().ldp_phased_ld(st.ctypes.data_as(ctypes.c_void_p), n, _ptr(r2, ctypes.c_double), _ptr(d, ctypes.c_double), _ptr(dp, ctypes.c_double),
+                             _ptr(neg, ctypes.c_uint8))
+    if rc != LDP_OK:
+        raise LdpError(rc, "ldp_phased_ld failed")
+    return tuple(a[:n].reshape(st.shape) for a in (r2, d, dp, neg))
 
 
 def synth_genotypes_host(seed, first_variant, n_variants, founder_ct, missing_rate=0.0):
@@ -646,6 +668,47 @@ class LdPruneEngine:
         self._ck(self._L.ldp_r2_unphased_hits(self._h, row_first, row_ct, float(min_r2), out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(found)))
         out = out[:min(found.value, capacity)]
         return out[np.lexsort((out["second"], out["first"]))], found.value
+
+    def r2_phased_stats_block(self, row_first, row_ct, col_first, col_ct, phase=None):
+        """ldp_r2_phased_stats_block: the five integers of --r2-phased for the pairs i < j of a dense block, (row_ct, col_ct) array of
+        PHASED_STATS_DTYPE; phase = the engine holding the phase-code rows, or None."""
+        out = np.zeros((row_ct, max(col_ct, 1)), dtype=PHASED_STATS_DTYPE)
+        self._ck(self._L.ldp_r2_phased_stats_block(self._h, phase._h if phase is not None else None, row_first, row_ct, col_first, col_ct,
+                                                   out.ctypes.data_as(ctypes.c_void_p), out.shape[1]))
+        return out[:, :col_ct]
+
+    def r2_phased_band_stats(self, row_first=0, row_ct=None, phase=None):
+        """ldp_r2_phased_band_stats: the same for the candidate pairs of second variants [row_first, row_first+row_ct), band order."""
+        row_ct = self.variant_ct - row_first if row_ct is None else row_ct
+        lo, _ = self.band()
+        j = np.arange(row_first, row_first + row_ct, dtype=np.int64)
+        n = int((j - lo[row_first:row_first + row_ct]).sum())
+        out = np.zeros(max(n, 1), dtype=PHASED_STATS_DTYPE)
+        self._ck(self._L.ldp_r2_phased_band_stats(self._h, phase._h if phase is not None else None, row_first, row_ct, out.ctypes.data_as(ctypes.c_void_p), n))
+        return out[:n]
+
+    def r2_phased_band_hits(self, min_r2, row_first=0, row_ct=None, phase=None, unsquared=False, capacity=1 << 20):
+        """ldp_r2_phased_band_hits: (stats, first, second, survivors found) of the band's pairs whose bound reaches min_r2, sorted by
+        (first, second); found > len(stats) means the buffers were too small."""
+        row_ct = self.variant_ct - row_first if row_ct is None else row_ct
+        st = np.zeros(max(capacity, 1), dtype=PHASED_STATS_DTYPE)
+        first = np.zeros(max(capacity, 1), dtype=np.uint32)
+        second = np.zeros(max(capacity, 1), dtype=np.uint32)
+        found = ctypes.c_uint64()
+        self._ck(self._L.ldp_r2_phased_band_hits(self._h, phase._h if phase is not None else None, row_first, row_ct, float(min_r2), 1 if unsquared else 0,
+                                                 st.ctypes.data_as(ctypes.c_void_p), _ptr(first, ctypes.c_uint32), _ptr(second, ctypes.c_uint32), capacity,
+                                                 ctypes.byref(found)))
+        k = min(found.value, capacity)
+        order = np.lexsort((second[:k], first[:k]))
+        return st[:k][order], first[:k][order], second[:k][order], found.value
+
+    def phased_filter(self):
+        """the last r2_phased_* call: 'pairs_seen' / 'pairs_dropped' by the device-side filter, 'ms_hethet' / 'ms_tuples' device time of the
+        double-heterozygote product and of the six-integer launches (ldp_debug_get_phased_filter)."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        x, y = ctypes.c_double(), ctypes.c_double()
+        self._ck(self._L.ldp_debug_get_phased_filter(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(x), ctypes.byref(y)))
+        return {"pairs_seen": int(a.value), "pairs_dropped": int(b.value), "ms_hethet": float(x.value), "ms_tuples": float(y.value)}
 
     def set_variants_vcor(self, chr_idx, bps, bp_radius, var_ct_radius=0x7fffffff):
         """Windowed plan of the --r2-unphased table (--ld-window-kb / --ld-window)."""

@@ -501,6 +501,55 @@ hipError_t launch_x_weighted(const XWeightedArgs& a, hipStream_t stream);
 hipError_t launch_pair_wide(const PairKernelArgs& a, hipStream_t stream, bool sparse = false);
 uint32_t pair_mfma_ksteps(uint32_t founder_ct);  // 64-sample k-steps per row (the unit of counters[2])
 
+// ---- --r2-phased: the double-heterozygote product and the five integers of a pair (ldp_pair_phased.hip) ------------------------
+// H[j][i] = sum over samples of e_j e_i with e = (code == 01): the samples heterozygous at both variants -- on the rows of a phase
+// engine (include/ldprune_hip.h: ldp_r2_phased_stats_block) the samples phased at neither.  One workgroup of four waves owns 64 x 64
+// pairs: second variants [jv, jv + 64) x first variants [vv, vv + 64), one 32 x 32 block product per wave, four staged row-blocks.
+struct HetHetItem {
+  uint32_t jv, vv;
+};
+struct HetHetArgs {
+  const uint8_t* codes;          // the resident 2-bit image, n_local rows
+  uint64_t code_row_bytes;
+  uint32_t founder_ct;
+  uint32_t n_local;
+  const uint32_t* lo;            // window start per variant (pairs i < lo[j] are not stored); nullptr: 0
+  const HetHetItem* items;
+  uint32_t n_items;
+  uint32_t row_first, row_end;   // only second variants j in [row_first, row_end) ...
+  uint32_t col_first, col_end;   // ... and first variants i in [col_first, col_end), i < j, are stored:
+  uint32_t* out;                 // out[(j - row_first) * ld + (i - col_first)]
+  uint64_t ld;
+};
+hipError_t launch_hethet(const HetHetArgs& a, hipStream_t stream);
+// The six integers and H of the genotype engine (tg, hg) and of the phase engine (tp, hp; nullptr: no phase rows) of a dense chunk
+// [rows][cols] (row q = second variant row_first + q, column c = first variant col_first + c) -> ldp_phased_stats_t of every pair
+// i < j (i >= lo[j] when lo != nullptr), written dense (out_ld != 0: out[q * out_ld + c]), in band order (pair_off != nullptr:
+// out[pair_off[j] - band_base + (i - lo[j])]) or, with hit_count != nullptr, appended to hit_* when the pair's bound reaches min_r2.
+struct PhasedCombineArgs {
+  const ldp_pair_stats_t* tg;
+  const uint32_t* hg;
+  const ldp_pair_stats_t* tp;
+  const uint32_t* hp;
+  const ldp_variant_rec* recs_g;  // flags bit 0 of both engines' records: the orientation the tuples are in
+  const ldp_variant_rec* recs_p;
+  const uint32_t* lo;
+  uint32_t rows, cols, row_first, col_first;
+  uint32_t founder_ct;
+  ldp_phased_stats_t* out;
+  uint64_t out_ld;
+  const uint64_t* pair_off;
+  uint64_t band_base;
+  ldp_phased_stats_t* hit_stats;
+  uint32_t* hit_first;
+  uint32_t* hit_second;
+  uint64_t hit_capacity;
+  unsigned long long* hit_count;  // [0] survivors, [1] pairs seen, [2] pairs dropped (all added to)
+  double min_r2;
+  uint32_t unsquared;
+};
+hipError_t launch_phased_combine(const PhasedCombineArgs& a, hipStream_t stream);
+
 // LDS rows of a work item that stages `units` 8-distance units starting at distance d0 (make_geom in the kernel)
 inline uint32_t tile_rows(uint32_t d0, uint32_t units) {
   const uint32_t dmax = d0 + 8 * units - 1;

@@ -210,6 +210,13 @@ struct EngineOptions {
 
 constexpr uint32_t kStageSlots = 4;  // pinned staging ring of host-memory input
 
+// the last ldp_r2_phased_* call of an engine (ldp_engine_phased.cpp): pairs its device-side filter saw / dropped, device time of the
+// double-heterozygote product and of the six-integer launches
+struct PhasedFilterStats {
+  uint64_t seen = 0, dropped = 0;
+  double ms_hethet = 0.0, ms_tuples = 0.0;
+};
+
 struct ldp_engine {
   ldp_params P;
   EngineOptions opt;
@@ -389,6 +396,7 @@ struct ldp_engine {
   uint64_t dec_next_offset = 0;        // ... and the file offset right behind that call's last record
 
   ldp_counters ctr;
+  PhasedFilterStats phased_last;
   // ldp_restrict_variants(): the last call's compaction (ldp_debug_get_compact_stats)
   uint64_t rows_compacted = 0, rows_direct = 0, rows_bounced = 0;
   double ms_compact = 0.0;
@@ -483,6 +491,10 @@ int begin_load_epoch(ldp_engine* e);
 inline size_t tile_counts_pin_offset(const ldp_engine* e) { return 4 + ((e->groups.size() + 1) * sizeof(uint32_t) + 7) / 8; }
 hipError_t queue_route(ldp_engine* e, size_t slot, hipStream_t stream, int allow_sparse, uint32_t row_end);
 int launch_ready_groups(ldp_engine* e);
+// ldp_engine_r2.cpp: rows of the all-pairs plan (r^2, or with as_float 2 the six integers of every pair, on request left on the device)
+struct HitRequest;
+int r2_rows_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_float, void* out, uint64_t ld_elems, const HitRequest* hits, uint32_t col_first = 0,
+                 uint32_t col_end = 0xffffffffu, bool out_on_device = false, bool band_plan_too = false);
 }  // namespace ldph
 
 // ldp_engine_load.cpp (defined inside its extern "C" block)

@@ -212,12 +212,14 @@ int r2_band_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_floa
 // rows [row_first, row_first+row_ct) of the all-pairs plan: dense into `out` (hits == nullptr) or filtered into hits->out
 // as_float 2: the six integers of every pair (ldp_pair_stats_t) instead of their r^2; out_on_device: `out` is device memory of this
 // engine's device (left there, no diagonal: the chrX-weighted r^2 below combines two engines' tuples on the device)
-int r2_rows_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_float, void* out, uint64_t ld_elems, const HitRequest* hits,
-                 uint32_t col_first = 0, uint32_t col_end = 0xffffffffu, bool out_on_device = false) {
+// band_plan_too (the --r2-phased calls, ldp_engine_phased.cpp; tuples only): a windowed plan (ldp_set_variants_vcor) is taken as well -- the kernels
+// drop the pairs in front of a second variant's window start, so the dense chunk holds the band's pairs and zeros; no 8 x 8 tiles then
+int r2_rows_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_float, void* out, uint64_t ld_elems, const HitRequest* hits, uint32_t col_first, uint32_t col_end,
+                 bool out_on_device, bool band_plan_too) {
   if (!e) {
     return LDP_ERR_INVALID;
   }
-  if (!e->planned || !e->matrix_mode) {
+  if (!e->planned || !(e->matrix_mode || (band_plan_too && e->band_r2_mode && (as_float == 2) && !hits))) {
     return fail(e, LDP_ERR_STATE, "ldp_set_variants_matrix() first");
   }
   if (hits) {
@@ -347,7 +349,7 @@ int r2_rows_impl(ldp_engine* e, uint32_t row_first, uint32_t row_ct, int as_floa
   hipError_t krc;
   if (on_mfma) {
     const std::vector<std::pair<uint32_t, uint32_t>> runs(1, std::make_pair(0u, e->local_ct));
-    rc = attach_mfma_plan(e, &A, runs, nullptr, row_first, row_end, &mf_buf, &mf_products, col_first, col_end, &tile_buf, &tile_products);
+    rc = attach_mfma_plan(e, &A, runs, nullptr, row_first, row_end, &mf_buf, &mf_products, col_first, col_end, e->matrix_mode ? &tile_buf : nullptr, &tile_products);
     if (rc) {
       return rc;
     }

@@ -215,11 +215,12 @@ bool parse_command_flags(Args& A, ArgCursor& c, const std::string& f) {
       die(8, "Error: Invalid %s r^2 threshold '%s'.\n", fl, par[next].c_str());
     }
     A.have_prune = true;
-  } else if ((f == "--r2-unphased") || (f == "--r-unphased")) {
+  } else if ((f == "--r2-unphased") || (f == "--r-unphased") || (f == "--r2-phased") || (f == "--r-phased")) {
     if (A.have_r2) {
       die(8, "Error: --r-phased, --r-unphased, --r2-phased, and --r2-unphased are mutually\nexclusive.\n");
     }
-    A.r_unsquared = (f == "--r-unphased");
+    A.r2_phased = (f == "--r2-phased") || (f == "--r-phased");
+    A.r_unsquared = (f == "--r-unphased") || (f == "--r-phased");
     g_r_unsquared = A.r_unsquared;
     // [{square | square0 | triangle | inter-chr}] ['yes-really'] [{zs | bin | bin4}] ... (plink2.cc:11090-11210)
     while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) {
@@ -249,7 +250,7 @@ bool parse_command_flags(Args& A, ArgCursor& c, const std::string& f) {
         A.r2_cols_given = true;
         A.r2_cols_desc = m.substr(5);
       }
-      else if ((m == "d") || (m == "dprime") || (m == "dprime-signed")) {
+      else if ((!A.r2_phased) && ((m == "d") || (m == "dprime") || (m == "dprime-signed"))) {
         die(8, "Error: --r2-unphased does not support computation of D or D'. Use --r2-phased\nwith 'cols=+%s' instead.\n", (m == "d") ? "d" : ((m == "dprime") ? "dprimeabs" : "dprime"));
       }
       else die(63, "Error: --r2-unphased modifier '%s' is not supported by plink2-hip (matrix shapes with bin/bin4, or the default-column table).\n", m.c_str());
@@ -263,12 +264,21 @@ bool parse_command_flags(Args& A, ArgCursor& c, const std::string& f) {
     if (A.r2_cols_given) {  // plink2.cc:11158-11172
       A.r2_cols = parse_col_descriptor(A.r2_cols_desc, {"chrom", "pos", "id", "ref", "alt1", "alt", "maybeprovref", "provref", "maj", "nonmaj", "freq", "d", "dprime", "dprimeabs"},
                                        default_cols, A.r_unsquared ? "r-unphased" : "r2-unphased");
-      if (A.r2_cols & (kVcorColD | kVcorColDprime | kVcorColDprimeAbs)) {
+      if ((!A.r2_phased) && (A.r2_cols & (kVcorColD | kVcorColDprime | kVcorColDprimeAbs))) {
         die(8, "Error: --r2-unphased does not support computation of D or D'. Use --r%s-phased\ninstead.\n", A.r_unsquared ? "" : "2");
       }
     }
     if ((A.r2_inter || A.r2_cols_given) && (A.r2_shape >= 0)) {
       die(8, "Error: Matrix-only and table-only --r2-unphased settings cannot be used together.\n");  // plink2.cc:11187-11191
+    }
+    if (A.r2_phased) {
+      // the phased statistics come as the windowed table only (p2h_r2_phased.cpp)
+      if (A.r2_shape >= 0) {
+        die(63, "Error: %s matrix shapes (square / square0 / triangle, bin / bin4) are not supported by plink2-hip: the windowed table only.\n", f.c_str());
+      }
+      if (A.r2_inter) {
+        die(63, "Error: %s inter-chr is not supported by plink2-hip: the windowed table only.\n", f.c_str());
+      }
     }
     A.r2_table = (A.r2_shape < 0);
     A.r2_text = (A.r2_shape >= 0) && (A.r2_float < 0);  // shape without bin/bin4: tab-delimited text matrix
@@ -877,6 +887,12 @@ void check_flag_combinations(Args& A) {
   }
   if (A.gpus < 1) {
     die(8, "Error: --gpus must be positive.\n");
+  }
+  if (A.r2_phased && (A.parallel_tot != 1)) {
+    die(63, "Error: --parallel with --r2-phased / --r-phased is not supported by plink2-hip.\n");
+  }
+  if (A.r2_phased && (A.gpus > 1)) {
+    die(63, "Error: --gpus above 1 with --r2-phased / --r-phased is not supported by plink2-hip.\n");
   }
 }
 

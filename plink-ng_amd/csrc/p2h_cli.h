@@ -154,6 +154,7 @@ struct Args {
   bool r2_ref_based = false;
   bool r2_allow_ambiguous = false;
   bool r_unsquared = false;        // --r-unphased: r = +-sqrt(r^2) with the sign of the covariance
+  bool r2_phased = false;          // --r2-phased / --r-phased: haplotype-frequency r^2, D, D' (windowed table only; p2h_r2_phased.cpp)
   uint32_t r2_cols = 0;            // kVcorCol* (set after the modifiers are read: plink2.cc:11158-11207)
   std::string r2_cols_desc;        // the text behind cols=
   bool r2_cols_given = false;
