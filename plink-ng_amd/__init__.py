@@ -20,7 +20,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 BIN_DIR = os.path.join(_HERE, "bin")
 LIB_PATH = os.path.join(LIB_DIR, "libldprune_hip.so")
-# the measurement build (-DLDP_MEASURE, csrc/ldp_env.h): environment presets, timing prints and the ablation kernels of tools/ --
+# the measurement build (-DLDP_MEASURE, csrc/ldp_env.h): environment presets, timing prints and the timed tile kernel of tools/attribution.py --
 # never loaded by tests/, bench.py's default run or plink2-hip; LDP_LIB_MEASURE=1 makes lib() load it (tools/attribution.py)
 MEASURE_LIB_PATH = os.path.join(LIB_DIR, "libldprune_hip_measure.so")
 CLI_PATH = os.path.join(BIN_DIR, "plink2-hip")

@@ -298,14 +298,14 @@ struct PairKernelArgs {
   // workgroup, and the deferred order costs it 3 % (config 5's density: 115.1 against 118.3 ms); nullptr: wd_tiles serves both
   const MfmaTile* wd_tiles_plain;
   uint32_t n_wd_tiles_plain;
-  uint32_t wd_sparse;            // the tiles also own the launch on the kRouteSparse route (pair_mfma_wide_kernel<., SPARSE>; EngineOptions::wide_sparse):
+  uint32_t wd_sparse;            // the tiles also own the launch on the kRouteSparse route (pair_mfma_wide_kernel<SPARSE>; EngineOptions::wide_sparse):
                                  // pair_mfma_kernel<., SPARSE = true> then skips the workgroups of their subcontigs as the complete-data kernel does
   uint32_t wd_diag_split;        // complete-data prune launches: the tiles on the diagonal take the kernel's 2 x 3 body (kWdDiagMap: 2 x 3 rectangles on all eight
                                  // waves), picked per workgroup (EngineOptions::wide_diag_kernel)
   uint32_t wd_diag_corner;       // ... and take the corner product of the distance-1 tile of their J tile (kWdDiagCornerWave; EngineOptions::wide_diag_corner);
                                  // only with wd_diag_split
   // per-tile routing (tile_route_kernel, queued behind route_kernel; EngineOptions::tile_route): the routed copies of wd_tiles (launch order) for
-  // pair_mfma_wide_kernel<0, false> and <0, true>, and of wd_tiles_plain (of wd_tiles where that is null) for pair_mfma_tile4_kernel.  The launchers
+  // pair_mfma_wide_kernel<false> and <true>, and of wd_tiles_plain (of wd_tiles where that is null) for pair_mfma_tile4_kernel.  The launchers
   // hand each kernel its copy in wd_tiles / wd_tiles_plain; with the flag set the complete-data tile kernel runs whatever the group word says, the
   // SPARSE one unless the word is kRouteComplete, the quarter tiles only on kRouteGeneral (a tile's class never exceeds the word).
   uint32_t wd_tile_route;

@@ -269,7 +269,7 @@ struct ldp_engine {
     uint32_t wd_first = 0, wd_ct = 0;    // ... and as wide-band tiles (wd_tiles)
     uint32_t wl_first = 0, wl_ct = 0;    // ... in launch order (wd_launch: eight XCD streams, padded to equal length)
     bool four_tiles = false;             // the group's last launch queued pair_mfma_tile4_kernel for them
-    bool sparse_tiles = false;           // ... and pair_mfma_wide_kernel<., SPARSE> (the tiles on the route of rows with a few missing calls)
+    bool sparse_tiles = false;           // ... and pair_mfma_wide_kernel<SPARSE> (the tiles on the route of rows with a few missing calls)
     bool tile_routed = false;            // ... with a class per tile (tile_route_kernel)
     bool launched = false;
     hipEvent_t ev_ready = nullptr;
@@ -348,7 +348,7 @@ struct ldp_engine {
   uint64_t csr_capacity = 0;
   unsigned long long* d_csr_counter = nullptr;
   uint8_t* d_stored_inv = nullptr;  // per local row: 1 = the image row is stored inverted relative to the input (codes_kernel, ldp_device.h)
-  bool wd_diag_lower = false;       // every diagonal tile's live products lie inside the 2 x 3 rectangles of pair_mfma_wide_kernel<., false, 3> (build_shard)
+  bool wd_diag_lower = false;       // every diagonal tile's live products lie inside the 2 x 3 rectangles of pair_mfma_wide_kernel<false> (wide_tile<false, 3>) (build_shard)
   bool any_stored_inv = false;      // some load may have inverted rows since the flags were last cleared
   uint32_t ctr_csr_overflows = 0;  // runs that fell back to the dense rows (test hook: option "csr_capacity")
   unsigned long long* h_counters_pin = nullptr;  // pinned: a pageable destination would make the 'async' copy block the host

@@ -61,24 +61,12 @@ __device__ __forceinline__ uint32_t wd_swizzle(uint32_t row) { return (row >> 1)
 // eight waves' worth of state hipcc spilled inside the stage loop for it, and a scratch reload's vmcnt wait drains the DMA
 // ring.  A wave's eight products sit next to each other in distance, so they mostly die together anyway; the products of a
 // partly live wave that hold no candidate pair accumulate numbers nobody reads.)
-// ABL != 0 exists in the MEASUREMENT build only (-DLDP_MEASURE, csrc/ldp_env.h; the shipped library instantiates <0> and nothing
-// else): ablations for the attribution tables of profiles/r04_experiments.md and r05_experiments.md.  Bits 0-3 make the results
-// WRONG by construction.  Bit 0 (value 1) = no DMA after the ring's first fill, bit 1 (2) = expand only the first k-step's operands
-// and reuse them (a quarter of the VALU work, the same operand statistics), bit 2 (4) = no LDS reads in the loop (every lane
-// multiplies what the first stage left in its registers' place), bit 3 (8) = no s_waitcnt vmcnt / s_barrier in the stage loop (the
-// waves run free), bit 4 (16) = no per-pair epilogue, bit 5 (32) = time stamps around the phases of every wave (results right:
-// where the cycles go), summed into g_wide_measure, bit 6 (64) = every tile stages the same 512 rows (wrong results; all of the DMA's
-// requests hit the L2: what the HBM leg of the traffic costs).
 // GC: the allele-count coding of complete rows (ldp_mfma_device.h); false: the +-2 coding, where a missing call is 0 and the
 // accumulators hold the exact dot product (the SPARSE instantiation below)
 // VC: V blocks of the wave's rectangle -- 4 (the tiles' 2 x 4 rectangles) or 3 (the diagonal tiles' kernel: 2 x 3, see pair_mfma_wide_kernel)
-template <int ABL, bool GC, int VC>
+template <bool GC, int VC>
 __device__ __forceinline__ void wide_stage(const mf_u4* __restrict__ st4, const uint32_t (&joff)[2], const uint32_t (&voff)[VC], uint32_t oH, uint32_t oR,
                                            mf_v16f (&acc)[2 * VC]) {
-  if constexpr ((ABL & 4) != 0) {
-    // (handled by wide_stage_kept below)
-    return;
-  }
   mf_u4 vH[2], vR[2];
   vH[0] = st4[voff[0] + oH];
   vR[0] = st4[voff[0] + oR];
@@ -88,11 +76,7 @@ __device__ __forceinline__ void wide_stage(const mf_u4* __restrict__ st4, const 
     opaque(H, R);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if ((ABL & 2) && ks) {
-        fj0[ks] = fj0[0];
-      } else {
-        fp4_expand<GC>(H[ks], R[ks], fj0[ks]);
-      }
+      fp4_expand<GC>(H[ks], R[ks], fj0[ks]);
     }
   }
   {
@@ -100,11 +84,7 @@ __device__ __forceinline__ void wide_stage(const mf_u4* __restrict__ st4, const 
     opaque(H, R);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if ((ABL & 2) && ks) {
-        fj1[ks] = fj1[0];
-      } else {
-        fp4_expand<GC>(H[ks], R[ks], fj1[ks]);
-      }
+      fp4_expand<GC>(H[ks], R[ks], fj1[ks]);
     }
   }
   // rows of C = first variant (A operand: a V block), columns = second variant (B operand: a J block)
@@ -117,11 +97,7 @@ __device__ __forceinline__ void wide_stage(const mf_u4* __restrict__ st4, const 
   opaque(vH[B], vR[B]);                                        \
   _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {           \
     Frag fv;                                                   \
-    if ((ABL & 2) && ks) {                                     \
-      fv = fj1[(ks + (b)) & 3];                                \
-    } else {                                                   \
-      fp4_expand<GC>(vH[B][ks], vR[B][ks], fv);              \
-    }                                                          \
+    fp4_expand<GC>(vH[B][ks], vR[B][ks], fv);                  \
     acc[b] = mfma_pair<GC>(fv, fj0[ks], acc[b]);                    \
     acc[VC + (b)] = mfma_pair<GC>(fv, fj1[ks], acc[VC + (b)]);      \
   }
@@ -206,42 +182,8 @@ __device__ __forceinline__ void wide_stage_pair(const mf_u4* __restrict__ st4, c
   wide_stage_pf<GC, VC, false>(st4, joff, voff, oH1, oR1, oH1, oR1, fb0, fb1, fa0, fa1, acc);
 }
 
-// ABL bit 2: the stage without LDS reads -- every row-block's codes are the two pieces this lane read ONCE (real genotypes of the first
-// stage, the dwords rotated per block and k-step so that consecutive MFMAs still see different operands)
-template <int ABL>
-__device__ __forceinline__ void wide_stage_kept(mf_u4 H, mf_u4 R, mf_v16f (&acc)[8]) {
-  opaque(H, R);
-  Frag fj0[4], fj1[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    if ((ABL & 2) && ks) {
-      fj0[ks] = fj0[0];
-      fj1[ks] = fj1[0];
-    } else {
-      fp4_expand<true>(H[ks], R[ks], fj0[ks]);
-      fp4_expand<true>(R[ks], H[(ks + 1) & 3], fj1[ks]);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    mf_u4 vH = {H[b & 3], H[(b + 1) & 3], H[(b + 2) & 3], H[(b + 3) & 3]}, vR = {R[(b + 2) & 3], R[(b + 3) & 3], R[b & 3], R[(b + 1) & 3]};
-    opaque(vH, vR);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      Frag fv;
-      if ((ABL & 2) && ks) {
-        fv = fj1[(ks + b) & 3];
-      } else {
-        fp4_expand<true>(vH[ks], vR[ks], fv);
-      }
-      acc[b] = mfma_pair<true>(fv, fj0[ks], acc[b]);
-      acc[4 + b] = mfma_pair<true>(fv, fj1[ks], acc[4 + b]);
-    }
-  }
-}
-
 #ifdef LDP_MEASURE
-// what the waves of the measured launches spent where (shader cycles, summed over waves; ABL bit 5 fills 0-5 and 9-10, every measured
+// what the waves of the measured launches spent where (shader cycles, summed over waves; the TIMED instantiation fills 0-5 and 9-10, every
 // instantiation 6-8): [0] s_waitcnt vmcnt in front of the stage barrier, [1] the stage barrier itself, [2] stages of waves with a live
 // product (DMA issue + LDS reads + expansions + MFMA issue), [3] stages of waves with none, [4] checkpoints, [5] epilogue, [6] entry to
 // exit, [7] waves, [8] entry to exit in 100 MHz wall ticks (shader clock = 100 MHz x [6] / [8]), [9] / [10] stage visits live / dead;
@@ -354,9 +296,12 @@ __device__ __forceinline__ uint32_t wide_sparse_round(const PairKernelArgs& A, c
 // section 4): as a launch of its own behind the others the diagonal tiles lose the L2 sharing with their neighbours (the share 339 against 273 ms
 // of pair kernels); inside the one launch 266.7 against 273.3 ms.  2 x 2 quads for tiles with at most eight live quads (the far tile of a J tile)
 // were built too and bought nothing: those tiles are bound by their staging, not by the matrix pipe.
-template <int ABL, bool SPARSE, int VC>
+// TIMED (the measurement build only, -DLDP_MEASURE, csrc/ldp_env.h; the shipped library instantiates nothing with it): time stamps around the phases of
+// every wave, summed into g_wide_measure -- where the cycles go.  Complete data, every tile in the 2 x 4 body; the results stay right.
+template <bool SPARSE, int VC, bool TIMED = false>
 __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __restrict__ lds, uint32_t* __restrict__ s_need, const MfmaTile* __restrict__ tile) {
-  static_assert((VC == 4) || ((VC == 3) && !SPARSE && (ABL == 0)), "2 x 4 rectangles, or the diagonal tiles' 2 x 3");
+  static_assert(!(TIMED && SPARSE), "the timed form is the complete-data kernel's");
+  static_assert((VC == 4) || ((VC == 3) && !SPARSE && !TIMED), "2 x 4 rectangles, or the diagonal tiles' 2 x 3");
   constexpr uint32_t NP = 2 * VC;              // products per wave
   constexpr uint32_t kColMask = (1u << VC) - 1u;
 #ifdef LDP_MEASURE
@@ -378,7 +323,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
   // tile of the same J tile, in a slot of its corner wave that is otherwise beyond the plan.  The distance-1 tile drops it here and retires with
   // the far tiles; `corner`: this (diagonal) tile has taken it.
   bool corner = false;
-  if constexpr ((ABL == 0) && !SPARSE) {
+  if constexpr (!TIMED && !SPARSE) {
     const uint32_t pad = __builtin_amdgcn_readfirstlane(tile->pad);
     if constexpr (VC == 3) {
       corner = A.wd_diag_corner && ((pad & kWdPadCornerTaken) != 0);
@@ -470,9 +415,6 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
     const uint32_t T = wave + kWdWaves * t;
     const uint32_t slot = T / kWdInstrPerBlock;
     uint32_t first = static_cast<uint32_t>(slot_first(slot));
-    if constexpr ((ABL & 64) != 0) {
-      first = slot * kMfBlock;  // (measurement: every tile of the launch stages the SAME 512 rows -- the DMA's L2 -> LDS leg without its HBM leg)
-    }
     first = (first < A.n_local) ? first : (A.n_local - 1);  // (a block beyond the rows is never live; keep its address legal anyway)
     first = __builtin_amdgcn_readfirstlane(first);
     base_t[t] = A.codes + static_cast<uint64_t>(first) * row_bytes;
@@ -490,7 +432,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
     }
     return m;
   };
-  uint32_t mine = (ABL & 1) ? 0u : count_mine();  // DMA wave-instructions per stage this wave issues
+  uint32_t mine = count_mine();  // DMA wave-instructions per stage this wave issues
 
   uint32_t joff[2], voff[VC];  // uint4 index of the row-block's first slot
 #pragma unroll
@@ -527,7 +469,6 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
     }
   }
 
-  mf_u4 keptH = {0, 0, 0, 0}, keptR = {0, 0, 0, 0};  // (ABL bit 2 only)
   uint32_t next_cp = 0;
   const uint32_t n_cp = A.cp_stats ? A.n_checkpoints : 0;
   const uint32_t live0 = live;        // the products of the plan
@@ -538,7 +479,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
 #pragma unroll
     for (int t = 0; t < static_cast<int>(kWdDma); ++t) {
       const uint32_t T = wave + kWdWaves * t;
-      if (((wg_need >> (T / kWdInstrPerBlock)) & 1u) && (!(ABL & 1) || (s < kWdMaxStages))) {  // (ABL bit 0: only the ring's first fill leaves HBM: what the DMA costs)
+      if ((wg_need >> (T / kWdInstrPerBlock)) & 1u) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base_t[t] + kbyte + src_off[t]),
                                          (__attribute__((address_space(3))) void*)(dst + T * 256), 16, 0, 0);
       }
@@ -566,10 +507,14 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
   for (uint32_t kc = 0; kc < n_stages;) {
     const uint32_t kc_end = issue_limit;  // the next checkpoint (or the end of the rows)
     for (; kc < kc_end; ++kc) {
+      if constexpr (!TIMED) {
+        wait_dma_then_barrier(mine * (issued - kc - 1));
+      }
 #ifdef LDP_MEASURE
       unsigned long long m_s0 = 0;
-      if constexpr ((ABL & 32) != 0) {
-        // (a two-stage ring: the stage about to be read is the only one in flight, the wait is always vmcnt(0))
+      if constexpr (TIMED) {
+        // the same wait with a time stamp on either side of its halves (a two-stage ring: the stage about to be read is the only one in flight, the wait
+        // is always vmcnt(0))
         const unsigned long long a0 = wd_clk();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned long long a1 = wd_clk();
@@ -577,11 +522,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
         m_s0 = wd_clk();
         m_t[0] += a1 - a0;
         m_t[1] += m_s0 - a1;
-      } else if constexpr ((ABL & 8) == 0) {
-        wait_dma_then_barrier(mine * (issued - kc - 1));
       }
-#else
-      wait_dma_then_barrier(mine * (issued - kc - 1));
 #endif
       if (issued < issue_limit) {
         dma_stage(issued, issue_buf);  // (reuses the buffer every wave finished reading before the barrier)
@@ -590,28 +531,19 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
       }
       const mf_u4* __restrict__ st4 = reinterpret_cast<const mf_u4*>(lds + read_buf * stage_dwords);
       read_buf = (read_buf + 1 == stages) ? 0 : read_buf + 1;
-      if constexpr (((ABL & 4) != 0) && (VC == 4)) {
-        if (kc == 0) {
-          keptH = st4[joff[0] + oH0];
-          keptR = st4[joff[0] + oR0];
-        }
-        if (live) {
-          wide_stage_kept<ABL>(keptH, keptR, acc);
-          wide_stage_kept<ABL>(keptR, keptH, acc);
-        }
-      } else if (live) {
-        if constexpr (((ABL & 6) == 0) && !SPARSE) {  // (measurement build: every ablation that leaves the stage's reads and expansions alone times THIS form)
+      if (live) {
+        if constexpr (!SPARSE) {
           // (the SPARSE instantiation keeps the two plain half-stages: measured with this form too -- 14 values parked in scratch, none inside a k-loop --
           // the slice at 0.1 % / 0.3 % missing calls 33.35 / 33.30 against 33.30 / 33.40 ms and 40.27 / 40.23 against 40.43 / 40.39 ms of pair kernels:
           // nothing; its waves wait for their +-2-coded operands' energy and for the interval checkpoints, not for the head of a half-stage)
           wide_stage_pair<true, VC>(st4, joff, voff, oH0, oR0, oH1, oR1, acc);
         } else {
-          wide_stage<ABL, !SPARSE, VC>(st4, joff, voff, oH0, oR0, acc);
-          wide_stage<ABL, !SPARSE, VC>(st4, joff, voff, oH1, oR1, acc);
+          wide_stage<false, VC>(st4, joff, voff, oH0, oR0, acc);
+          wide_stage<false, VC>(st4, joff, voff, oH1, oR1, acc);
         }
       }
 #ifdef LDP_MEASURE
-      if constexpr ((ABL & 32) != 0) {
+      if constexpr (TIMED) {
         m_t[live ? 2 : 3] += wd_clk() - m_s0;
         m_visits[live ? 0 : 1] += 1;
       }
@@ -625,7 +557,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
       break;
     }
 #ifdef LDP_MEASURE
-    const unsigned long long m_c0 = ((ABL & 32) != 0) ? wd_clk() : 0ull;
+    const unsigned long long m_c0 = TIMED ? wd_clk() : 0ull;
 #endif
     // ---- checkpoint (ldp_device.h): drop the products whose candidate pairs are all provably below the threshold ----
     __syncthreads();  // every wave is done with the last stage: LDS is scratch now
@@ -791,13 +723,13 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
     }
     if (all_need != wg_need) {
       wg_need = __builtin_amdgcn_readfirstlane(all_need);
-      mine = (ABL & 1) ? 0u : count_mine();
+      mine = count_mine();
     }
     issue_limit = (next_cp < n_cp) ? checkpoint_stage(next_cp) : n_stages;
     issued_base = kc;
     ring_fill();  // restart the ring at this stage
 #ifdef LDP_MEASURE
-    if constexpr ((ABL & 32) != 0) {
+    if constexpr (TIMED) {
       m_t[4] += wd_clk() - m_c0;
     }
 #endif
@@ -821,9 +753,6 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
   uint32_t n_true = 0;
 #ifdef LDP_MEASURE
   const unsigned long long m_e0 = wd_clk();
-  if constexpr ((ABL & 16) != 0) {
-    live = 0;  // (no per-pair epilogue: what it costs)
-  }
 #endif
 #pragma unroll
   for (int round = 0; round < 2; ++round) {
@@ -890,7 +819,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
     const unsigned long long m_clk1 = wd_clk(), m_wall1 = __builtin_amdgcn_s_memrealtime();
     m_t[5] = m_clk1 - m_e0;
     if (lane == 0) {
-      if constexpr ((ABL & 32) != 0) {
+      if constexpr (TIMED) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
           atomicAdd(&g_wide_measure[q], m_t[q]);
@@ -923,7 +852,7 @@ __device__ __forceinline__ void wide_tile(const PairKernelArgs& A, uint32_t* __r
 #endif
 }
 
-template <int ABL, bool SPARSE = false>
+template <bool SPARSE = false, bool TIMED = false>
 __global__ __launch_bounds__(kWdWaves * 64, 2) void pair_mfma_wide_kernel(PairKernelArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ uint32_t s_need[kWdWaves];
@@ -937,24 +866,24 @@ __global__ __launch_bounds__(kWdWaves * 64, 2) void pair_mfma_wide_kernel(PairKe
     return;
   }
   const MfmaTile* __restrict__ tile = A.wd_tiles + idx;
-  if constexpr ((ABL == 0) && !SPARSE) {
+  if constexpr (!TIMED && !SPARSE) {
     // a diagonal tile in 2 x 3 rectangles (block-uniform: two whole bodies side by side, each with its ONE form of the stage loop -- a second form
     // INSIDE a loop is what made hipcc spill in rounds 3-5)
     if (A.wd_diag_split && (tile->jv == tile->vv)) {
-      wide_tile<0, false, 3>(A, lds, s_need, tile);
+      wide_tile<false, 3>(A, lds, s_need, tile);
       return;
     }
   }
-  wide_tile<ABL, SPARSE, 4>(A, lds, s_need, tile);
+  wide_tile<SPARSE, 4, TIMED>(A, lds, s_need, tile);
 }
 
 // the 128 KiB ring is dynamic LDS above the default limit: the attribute once per instantiation, then the launch
-template <int ABL, bool SPARSE = false>
+template <bool SPARSE = false, bool TIMED = false>
 hipError_t wide_launch(const dim3& grid, const dim3& block, size_t lds, hipStream_t stream, const PairKernelArgs& a) {
   static const bool attr_set =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_mfma_wide_kernel<ABL, SPARSE>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) == hipSuccess;
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_mfma_wide_kernel<SPARSE, TIMED>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) == hipSuccess;
   (void)attr_set;
-  hipLaunchKernelGGL((pair_mfma_wide_kernel<ABL, SPARSE>), grid, block, lds, stream, a);
+  hipLaunchKernelGGL((pair_mfma_wide_kernel<SPARSE, TIMED>), grid, block, lds, stream, a);
   return hipGetLastError();
 }
 
@@ -980,18 +909,16 @@ hipError_t launch_pair_wide(const PairKernelArgs& a_in, hipStream_t stream, bool
   const dim3 grid(per_xcd * 8), block(kWdWaves * 64);
   if (sparse) {
     // the same tiles for launches whose rows have a few missing calls (route kRouteSparse)
-    return wide_launch<0, true>(grid, block, lds, stream, a);
+    return wide_launch<true>(grid, block, lds, stream, a);
   }
 #ifdef LDP_MEASURE
-  // LDP_DEBUG_WIDE_ABLATE (measurement build only; bits 0-3 give WRONG results): see wide_stage.  Read at every launch.
+  // LDP_DEBUG_WIDE_ABLATE=32 (measurement build only): the timed instantiation, see wide_tile; any other value is ignored.  Read at every launch.
   const char* v = LDP_ENV("LDP_DEBUG_WIDE_ABLATE");
-#define LDP_WD_CASE(n) case n: return wide_launch<n>(grid, block, lds, stream, a);
-  switch (v ? atoi(v) : 0) {
-    LDP_WD_CASE(1) LDP_WD_CASE(2) LDP_WD_CASE(4) LDP_WD_CASE(7) LDP_WD_CASE(8) LDP_WD_CASE(9) LDP_WD_CASE(15) LDP_WD_CASE(16) LDP_WD_CASE(25) LDP_WD_CASE(31) LDP_WD_CASE(32) LDP_WD_CASE(64)
+  if (v && (atoi(v) == 32)) {
+    return wide_launch<false, true>(grid, block, lds, stream, a);
   }
-#undef LDP_WD_CASE
 #endif
-  return wide_launch<0>(grid, block, lds, stream, a);
+  return wide_launch<false>(grid, block, lds, stream, a);
 }
 
 #ifdef LDP_MEASURE

@@ -55,23 +55,22 @@ def test_wide_band_kernel_has_one_branch_free_stage_loop_and_no_scratch(tmp_path
     cp = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--cuda-device-only", "-S",
                          src, "-o", str(out), "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert cp.returncode == 0, cp.stdout[-2000:]
-    # (the file also holds the measurement-only ablations pair_mfma_wide_kernel<1 | 2 | 4 | 7>; the product is <0>)
     usage = {}
     for chunk in cp.stdout.split("Function Name: ")[1:]:
         usage[chunk.split()[0]] = (int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", chunk).group(1)), int(re.search(r"VGPRs Spill: (\d+)", chunk).group(1)))
     assert usage, cp.stdout[-2000:]
     for name, (scr, spill) in usage.items():
-        if "pair_mfma_wide_kernelILi0ELb0E" in name:
+        if "pair_mfma_wide_kernelILb0ELb0E" in name:
             assert (scr <= 64) and (spill <= 16), (name, scr, spill)   # (outside the k-loops: checked below)
         else:
             assert (scr, spill) == (0, 0), (name, scr, spill)
     assert set(int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", cp.stdout)) == {2}
     text = open(out).read()
-    # <0, false>: complete data, the allele-count coding; <0, true>: the SPARSE instantiation (rows with a few missing calls: the +-2 coding,
+    # <false>: complete data, the allele-count coding; <true>: the SPARSE instantiation (rows with a few missing calls: the +-2 coding,
     # an interval checkpoint and epilogue with FP64 interval arithmetic and a whole-wave recount around the SAME stage loop)
     for sparse in (False, True):
-        m = re.search(r"^(_ZN3ldp\w*pair_mfma_wide_kernelILi0ELb%dE\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel" % int(sparse), text, re.S | re.M)
-        assert m, "pair_mfma_wide_kernel<0, %s> not found" % sparse
+        m = re.search(r"^(_ZN3ldp\w*pair_mfma_wide_kernelILb%dELb0E\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel" % int(sparse), text, re.S | re.M)
+        assert m, "pair_mfma_wide_kernel<%s> not found" % sparse
         lines = m.group(2).splitlines()
         mf = [k for k, ln in enumerate(lines) if "v_mfma_scale_f32_32x32x64_f8f6f4" in ln]
         # the copies of the stage body: runs of matrix instructions less than 300 lines apart.  SPARSE: one (two half-stages of 32).  Complete data: the

@@ -221,7 +221,7 @@ def test_a_few_missing_calls_parallelogram_plan(gpu_pkg, n, miss, r2, redraw, fr
 
 @pytest.mark.parametrize("case", SPARSE_WIDE_CASES)
 def test_a_few_missing_calls_on_the_tiles(gpu_pkg, case):
-    """pair_mfma_wide_kernel<0, SPARSE> (classify_sparse): late LD 37 rows back, rare variants whose partners miss calls on the carriers,
+    """pair_mfma_wide_kernel<SPARSE> (classify_sparse): late LD 37 rows back, rare variants whose partners miss calls on the carriers,
     complete rows, rows at 7 % missing"""
     m, n, window, step, is_bp, r2, order, min_reach, miss, adversarial = case
     raw, chr_idx, bps = sparse_wide_rows(case)

@@ -1,7 +1,7 @@
 """The r^2 outputs of complete-data launches, every value against an independent reference.
 
 A launch whose resident rows have no missing call at all runs pair_mfma_kernel<4, false, *> over the parallelogram plan and, once an all-pairs
-request reaches 12 row-blocks, pair_mfma_wide_kernel<0> over 8 x 8 block tiles.  Their r^2 epilogue (emit_pair behind r2_out / r2_hits: row and
+request reaches 12 row-blocks, pair_mfma_wide_kernel<false> over 8 x 8 block tiles.  Their r^2 epilogue (emit_pair behind r2_out / r2_hits: row and
 column clipping, dense or band index, float cast, NaN bit patterns, hit filter, six-integer tuples, signed r; the tiles' orientation fix-up and
 the planner's row / column filtering before it) is compared here pair by pair -- no sampling, no tolerance, bit patterns only -- with
 ldtools.band_pair_stats / band_r2 (float64 matrix products and ComputeR2's operations in numpy; tests/test_pair_reference.py checks them against
