@@ -333,6 +333,15 @@ int ldp_set_sample_map(ldp_engine* e, uint32_t raw_sample_ct, const uint32_t* sr
  * engine whose ldp_run() removes nothing.  LDP_ERR_UNSUPPORTED on a sharded engine (ldp_set_shard() with world > 1), after
  * LDP_GENO_PHASED loads and after loads through a sample map that is not a plain subset of the file's samples. */
 int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t kept_ct, const uint32_t* chr_idx, const uint32_t* bps);
+/* Per-sample missing-call counts from the resident image, for a host's --mind (LoadSampleMissingCts, plink2_data.cc:10846):
+ * out[s], s < founder_ct: the number of variants in [first_variant, first_variant + n) whose resident row has a missing call for
+ * sample s.  Indices are the engine's current ones (before or after ldp_restrict_variants()); n == 0 gives zeros.  One read of the
+ * rows on the engine's stream, which is synchronised before the call returns; nothing of the engine changes.  out: host memory,
+ * founder_ct entries.  LDP_ERR_STATE before every row of the range is loaded, LDP_ERR_INVALID for a range beyond variant_ct,
+ * LDP_ERR_UNSUPPORTED on engines that keep bit-planes (more founders than ldp_matrix_pipe_max_founders(), or "pair_mfma" 0), on
+ * sharded engines (world > 1), and after LDP_GENO_PHASED loads or loads through a sample map that makes het calls missing (the
+ * image's columns are not the samples' hardcalls there). */
+int ldp_sample_missing_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, uint32_t* out);
 /* major-allele frequencies (GetAlleleFreq(..., maj_alleles[v]), plink2_ld.cc:915) for LDP_GENO_INVERSE
  * input; for REF/BED input the engine derives them itself and this call overrides them. */
 int ldp_set_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, const double* maj_freqs);

@@ -70,6 +70,8 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
  *   "x_rows"          k: ldp_r2_unphased_block_x*() work in chunks of k rows
  *   "compact_batch_rows" k: ldp_restrict_variants() moves the image in batches of k rows (0 = as many as 256 MiB hold): which batches
  *                     are copied directly and which go through the bounce buffer depends on rows per batch
+ *   "sample_missing_slab_rows" k: ldp_sample_missing_counts() cuts its rows into slabs of k (at most 8160: 32 row lanes x the 255 an
+ *                     8-bit counter field holds); 0 = full slabs on a large image, shorter ones on a small image
  * Results never depend on these.  Unknown name: LDP_ERR_INVALID. */
 int ldp_debug_set_option(ldp_engine* e, const char* name, double value);
 /* The .pgen reader's phase / subset routines use pext / pdep where the host has BMI2; on != 0 forces the portable loops for the whole
@@ -105,6 +107,10 @@ int ldp_debug_tile_classes(ldp_engine* e, uint8_t* out, uint64_t capacity, uint3
  * stays where it is counts nowhere), and the device time of the image's compaction (HIP events on the engine's stream).  Any
  * pointer may be NULL. */
 int ldp_debug_get_compact_stats(const ldp_engine* e, uint64_t* rows_compacted, uint64_t* rows_direct, uint64_t* rows_bounced, double* ms_compact);
+
+/* What the last ldp_sample_missing_counts() did: the device time of its kernel launches (HIP events on the engine's stream) and the bytes
+ * of the image they read (rows x row pitch).  Any pointer may be NULL. */
+int ldp_debug_get_sample_missing_stats(const ldp_engine* e, double* ms_kernel, uint64_t* bytes_read);
 
 /* What the last ldp_r2_phased_* call on this engine did (ldp_counters has no room left for it): the pairs its device-side filter saw
  * and the pairs it dropped (both 0 for the calls that do not filter), and the device time, HIP events on the engine's stream, of the

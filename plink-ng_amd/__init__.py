@@ -111,14 +111,14 @@ CABI_SYMBOLS = [
     "ldp_debug_set_option", "ldp_pgen_debug_force_portable", "ldp_matrix_pipe_max_founders", "ldp_map_rows", "ldp_release_device", "ldp_debug_wide_plan",
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
-    "ldp_restrict_variants", "ldp_debug_get_compact_stats",
+    "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
 ]
 
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ("ldp_kernels.hip", "ldp_codes.hip", "ldp_pair_mfma.hip", "ldp_pair_wide.hip", "ldp_pred_csr.hip", "ldp_pgen_decode.hip", "ldp_synth.hip", "ldp_engine.cpp", "ldp_engine_run.cpp", "ldp_engine_r2.cpp",
-                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_pgen.cpp", "ldp_topology.cpp",
+                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
                                           "ldp_pair_phased.hip", "ldp_engine_phased.cpp", "ldp_phased_ld.cpp")]
 
 
@@ -234,6 +234,8 @@ def lib():
     L.ldp_release_device.argtypes = [vp]
     L.ldp_restrict_variants.argtypes = [vp, u64p, ctypes.c_uint32, u32p, u32p]
     L.ldp_debug_get_compact_stats.argtypes = [vp, u64p, u64p, u64p, f64p]
+    L.ldp_sample_missing_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p]
+    L.ldp_debug_get_sample_missing_stats.argtypes = [vp, f64p, u64p]
     L.ldp_load_pgen_records.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
                                         ctypes.POINTER(ldp_pgen_rec), ctypes.c_uint32, u32p]
     L.ldp_load_pgen_records_phased.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
@@ -866,6 +868,21 @@ class LdPruneEngine:
         ms = ctypes.c_double()
         self._ck(self._L.ldp_debug_get_compact_stats(self._h, ctypes.byref(n), ctypes.byref(d), ctypes.byref(b), ctypes.byref(ms)))
         return {"rows_compacted": int(n.value), "rows_direct": int(d.value), "rows_bounced": int(b.value), "ms_compact": float(ms.value)}
+
+    def sample_missing_counts(self, first=0, n=None, out=None):
+        """ldp_sample_missing_counts: per sample, the variants of [first, first + n) whose resident row has a missing call for it (uint32 array
+        of founder_ct entries; `out`: write there instead -- a uint32 array, its first founder_ct entries)."""
+        n = self.variant_ct - first if n is None else n
+        if out is None:
+            out = np.zeros(max(self.founder_ct, 1), dtype=np.uint32)
+        self._ck(self._L.ldp_sample_missing_counts(self._h, int(first), int(n), _ptr(out, ctypes.c_uint32)))
+        return out[:self.founder_ct]
+
+    def sample_missing_stats(self):
+        """the last sample_missing_counts(): 'ms_kernel' (HIP events) and 'bytes_read' (ldp_debug_get_sample_missing_stats)."""
+        ms, nb = ctypes.c_double(), ctypes.c_uint64()
+        self._ck(self._L.ldp_debug_get_sample_missing_stats(self._h, ctypes.byref(ms), ctypes.byref(nb)))
+        return {"ms_kernel": float(ms.value), "bytes_read": int(nb.value)}
 
     def release_device(self):
         """Free the engine's device memory, keep its plan (ldp_release_device)."""

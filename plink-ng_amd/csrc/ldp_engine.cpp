@@ -1721,6 +1721,8 @@ int ldp_debug_set_option(ldp_engine* e, const char* name, double value) {
     e->opt.x_rows = static_cast<uint32_t>(std::max(0.0, value));
   } else if (n == "compact_batch_rows") {
     e->opt.compact_batch_rows = static_cast<uint32_t>(std::min(std::max(0.0, value), 4294967295.0));
+  } else if (n == "sample_missing_slab_rows") {
+    e->opt.sample_missing_slab_rows = static_cast<uint32_t>(std::min(std::max(0.0, value), 4294967295.0));
   } else {
     return fail(e, LDP_ERR_INVALID, "unknown option: " + n);
   }

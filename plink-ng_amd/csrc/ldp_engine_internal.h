@@ -206,6 +206,7 @@ struct EngineOptions {
   bool decode_no_lds = false;  // "decode_no_lds" 1: decoded rows are assembled in global memory (what rows beyond 128 KiB take) instead of LDS
   uint32_t x_rows = 0;         // "x_rows" k: the chrX-weighted blocks in chunks of k rows
   uint32_t compact_batch_rows = 0;  // "compact_batch_rows" k: ldp_restrict_variants() moves the image in batches of k rows (0: as many as 256 MiB hold)
+  uint32_t sample_missing_slab_rows = 0;  // "sample_missing_slab_rows" k: ldp_sample_missing_counts() cuts the rows into slabs of k (0: by the image's size; at most 8160)
 };
 
 constexpr uint32_t kStageSlots = 4;  // pinned staging ring of host-memory input
@@ -400,6 +401,9 @@ struct ldp_engine {
   // ldp_restrict_variants(): the last call's compaction (ldp_debug_get_compact_stats)
   uint64_t rows_compacted = 0, rows_direct = 0, rows_bounced = 0;
   double ms_compact = 0.0;
+  // ldp_sample_missing_counts(): the last call's kernel time and the image bytes its launches read (ldp_debug_get_sample_missing_stats)
+  double ms_sample_missing = 0.0;
+  uint64_t sample_missing_bytes = 0;
   // a bit-plane engine that was restricted keeps the checkpoint statistics its rows were counted with -- and with them the checkpoints
   // of the plan they were loaded under (none for ldp_set_variants_matrix) -- until its device memory is released
   bool replan_keeps_image = false;  // set around the ldp_set_variants() of ldp_restrict_variants(): build_shard() frees the plan-sized device arrays only

@@ -542,6 +542,30 @@ bool parse_filter_flags(Args& A, ArgCursor& c, const std::string& f) {
       die(8, "Error: --max-maf requires a value.\n");
     }
     ((f == "--maf") ? A.min_maf : ((f == "--max-maf") ? A.max_maf : A.geno)) = d;
+  } else if (f == "--mind") {  // plink2.cc:8878-8913: [max missing rate] ['dosage'] ['hh-missing'], default 0.1; 1 is a no-op
+    double d = 0.1;
+    bool have_number = false;
+    uint32_t param_ct = 0;
+    // (a token that starts with '-' and goes on with a digit or '.' is a number, not a flag: plink2_cmdline.cc IsCmdlineFlagStart)
+    auto is_param = [](const char* t) { return (t[0] != '-') || ((t[1] >= '0') && (t[1] <= '9')) || (t[1] == '.'); };
+    while ((i + 1 < argc) && is_param(argv[i + 1])) {
+      const std::string v = argv[++i];
+      if (++param_ct > 2) {
+        die(8, "Error: --mind accepts at most 2 arguments.\n");
+      }
+      const char* endp = v.c_str();
+      if ((v == "dosage") || (v == "hh-missing")) {
+        die(63, "Error: the '%s' modifier of --mind is not supported by plink2-hip (hardcall missingness only).\n", v.c_str());
+      } else if (have_number) {
+        die(8, "Error: Invalid --mind argument sequence.\n");
+      } else if (!scan_double_plink(v.c_str(), &d, &endp) || *endp) {
+        die(8, "Error: Invalid --mind argument '%s'.\n", v.c_str());
+      } else if ((d < 0.0) || (d > 1.0)) {
+        die(8, "Error: Invalid --mind argument '%s' (must be in [0, 1]).\n", v.c_str());
+      }
+      have_number = true;
+    }
+    A.mind = d;
   } else if ((f == "--mac") || (f == "--max-mac")) {  // plink2.cc:8785-8867 (default mode: the non-major allele's dosage sum over the founders)
     if ((i + 1 >= argc) || (argv[i + 1][0] == '-')) {
       die(8, "Error: %s requires a value.\n", f.c_str());

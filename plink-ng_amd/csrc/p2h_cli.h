@@ -36,6 +36,7 @@ namespace p2h {
 constexpr double kSmallEpsilon = 0.00000000000005684341886080801486968994140625;  // 2^-44
 extern FILE* g_log;
 extern bool g_silent;       // --silent
+extern bool g_log_mute;     // logprintf() prints nothing (die() still does)
 extern bool g_r_unsquared;  // --r-unphased
 
 double now_s();
@@ -173,6 +174,7 @@ struct Args {
   // --maf / --max-maf (nonmajor-allele frequency over the founders) and --geno (missing-call rate over the samples), as the
   // reference enforces them (EnforceFreqConstraints plink2_filter.cc:3791, EnforceGenoThresh :3498); 0 / 1 / 1 = not given
   double min_maf = 0.0, max_maf = 1.0, geno = 1.0;
+  double mind = 1.0;  // --mind (missing-call rate of a sample over the variants the table filters leave; MindFilter plink2_filter.cc:3329); 1 = not given / no-op
   uint64_t min_allele_ddosage = 0, max_allele_ddosage = ~0ull;  // --mac / --max-mac in 32768ths of an allele copy (plink2.cc:8785-8867)
   bool ac_founders = false;
   uint32_t max_alleles = 0xffffffffu;  // --max-alleles N (applied while the variant table loads, LoadPvar)
@@ -242,8 +244,10 @@ struct DebugHooks {
 extern DebugHooks g_dbg;
 
 Args parse_args(int argc, char** argv);
+// (fid_present / sids: how the reference writes sample ID lists -- WriteSampleIds, plink2_common.cc:4219: an FID column when the file has one,
+// a .fam always; an SID column when the .psam has one, else *sids stays empty)
 void load_samples(const Args& A, std::vector<uint8_t>* is_founder, std::vector<uint8_t>* sex, std::vector<std::string>* fid_iid = nullptr,
-                  std::vector<std::pair<std::string, std::string>>* parents = nullptr);
+                  std::vector<std::pair<std::string, std::string>>* parents = nullptr, bool* fid_present = nullptr, std::vector<std::string>* sids = nullptr);
 
 struct Variants {
   std::vector<std::string> chrom, id;
@@ -538,6 +542,18 @@ struct Session {
   double host_filter_s = 0.0;
   uint32_t kept_sample_ct = 0;
   std::vector<uint8_t> inc_chr0;  // device_filter: 1 = inc[k] lies on chromosome 0 (empty or shorter than inc: the rest is 0)
+  // --mind (the sample-side counterpart).  load_inputs() decides it from a host pass over the rows, or leaves it to run_prune() (mind_device:
+  // the counts come from the resident image, ldp_sample_missing_counts; device_filter is set with it, so that every row the table filters leave
+  // is loaded under the all-pairs plan first).  A device-side decision that removes samples ends the run with `restart` set and the decision in
+  // mind_removed; main() then starts over with a session that has mind_decided set and the same mind_removed, which load_inputs() applies as
+  // --remove would have.
+  bool mind_device = false, mind_decided = false, restart = false;
+  std::vector<uint8_t> mind_removed;     // per sample of the file: 1 = removed by --mind
+  uint32_t mind_variant_ct = 0;          // the variants --mind counts over (table filters only: chromosome 0 and multiallelic variants included)
+  std::vector<std::string> sample_keys;  // "FID<tab>IID" per sample of the file (kept for <out>.mindrem.id)
+  std::vector<std::string> sample_sids;  // SID per sample when the .psam has the column
+  bool fid_present = true;
+  double t_begin_first = 0.0;            // restarted run: main()'s first start (the total of --timing covers both loads)
   // (... and, once the runtime is up, this thread -- the one that creates the engines, their copy threads and their pinned staging -- moves next to the device)
   void join_hip() {
     if (t_hip.joinable()) {
@@ -580,6 +596,12 @@ struct CountFilters {
 // --geno counts over the kept samples; one engine holds every row only with one GPU; the r^2 outputs, --clump and --indep-pairphase keep
 // the host's pass (their engines are planned before the load); dosage-based frequencies never reach the device.
 const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_samples, uint32_t founder_ct);
+
+// --mind's decision from per-sample missing-call counts (indexed by sample of the file; only kept samples are looked at): MindFilter's integer
+// rule, its log lines, <out>.mindrem.id; *removed: per sample of the file.  Returns the number of samples removed.
+uint32_t mind_decide(const Session& S, const std::vector<uint32_t>& missing_cts, std::vector<uint8_t>* removed);
+// ... applied: the removed samples are neither kept nor founders from here on; exit 13 when nobody is left (plink2.cc:1836-1838)
+void mind_apply(Session& S, const std::vector<uint8_t>& removed);
 
 void load_inputs(Session& S, int argc, char** argv);
 int run_r2(Session& S);

@@ -169,6 +169,57 @@ void count_rows(const uint8_t* rows, uint64_t stride, uint32_t n_rows, bool bed,
 }
 
 
+// One multi-threaded pass over the rows of the variants `todo` (raw indices, ascending) -- what --geno / --maf and --mind count from before the
+// variant list is final: fn(thread, rows, n, q) gets n rows, rec_bytes apart, of the variants todo[q .. q + n).  Fixed-width rows are read where
+// they lie in the mapping; variable-width records are decoded in runs of file-consecutive variants (ldp_pgen_read, all host threads) first.
+template <class F>
+static void for_each_row_run(ldp_pgen* pg, const std::string& gpath, const uint8_t* direct_rows, uint64_t rec_bytes, const std::vector<uint32_t>& todo, uint32_t nthreads, F fn) {
+  if (direct_rows) {
+    std::atomic<size_t> next(0);
+    const size_t kTask = 2048;
+    std::vector<std::thread> pool;
+    for (uint32_t t = 0; t < nthreads; ++t) {
+      pool.emplace_back([&, t]() {
+        for (size_t q0 = next.fetch_add(kTask); q0 < todo.size(); q0 = next.fetch_add(kTask)) {
+          const size_t q1 = std::min(todo.size(), q0 + kTask);
+          for (size_t q = q0; q < q1; ++q) {
+            fn(t, direct_rows + static_cast<uint64_t>(todo[q]) * rec_bytes, 1u, q);
+          }
+        }
+      });
+    }
+    for (std::thread& th : pool) {
+      th.join();
+    }
+    return;
+  }
+  const uint32_t max_run = std::max<uint32_t>(1, static_cast<uint32_t>((256ull << 20) / std::max<uint64_t>(rec_bytes, 1)));
+  std::vector<uint8_t> decoded;
+  for (size_t q0 = 0; q0 < todo.size();) {
+    uint32_t run = 1;
+    while ((q0 + run < todo.size()) && (todo[q0 + run] == todo[q0] + run) && (run < max_run)) {
+      ++run;
+    }
+    decoded.resize(static_cast<size_t>(run) * rec_bytes);
+    if (ldp_pgen_read(pg, todo[q0], run, decoded.data(), rec_bytes, 0)) {
+      die(6, "Error: %s: %s\n", gpath.c_str(), ldp_pgen_last_error(pg));
+    }
+    std::atomic<uint32_t> next(0);
+    std::vector<std::thread> pool;
+    for (uint32_t t = 0; t < nthreads; ++t) {
+      pool.emplace_back([&, t]() {
+        for (uint32_t r0 = next.fetch_add(256); r0 < run; r0 = next.fetch_add(256)) {
+          fn(t, decoded.data() + static_cast<uint64_t>(r0) * rec_bytes, std::min(256u, run - r0), q0 + r0);
+        }
+      });
+    }
+    for (std::thread& th : pool) {
+      th.join();
+    }
+    q0 += run;
+  }
+}
+
 CountFilters::CountFilters(const Args& args, uint32_t kept_samples) : A(args) {
   geno_on = (A.geno != 1.0);
   mac_on = (A.min_allele_ddosage != 0) || (A.max_allele_ddosage != ~0ull);
@@ -239,12 +290,207 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
   return nullptr;
 }
 
+// ---- --mind (LoadSampleMissingCts plink2_data.cc:10846-10990, MindFilter plink2_filter.cc:3329-3383)
+// per-sample missing hardcalls of rows: cts[sample of the file] += 1 for every kept sample (m_s: one 01 bit pair per kept sample) whose call is missing
+static void count_sample_missing(const uint8_t* rows, uint64_t stride, uint32_t n_rows, bool bed, uint32_t raw_sample_ct, const std::vector<uint64_t>& m_s, uint32_t* cts) {
+  const uint64_t kLo = 0x5555555555555555ull;
+  const uint64_t row_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
+  const size_t words = m_s.size();
+  for (uint32_t r = 0; r < n_rows; ++r) {
+    const uint8_t* row = rows + static_cast<uint64_t>(r) * stride;
+    for (size_t w = 0; w < words; ++w) {
+      uint64_t x = 0;
+      const uint64_t left = row_bytes - 8 * w;
+      memcpy(&x, row + 8 * w, (left < 8) ? left : 8);
+      // .pgen: 11 is missing; .bed: 01 (pgenlib_read.cc:2157)
+      uint64_t miss = (bed ? (x & ~(x >> 1)) : (x & (x >> 1))) & kLo & m_s[w];
+      while (miss) {
+        ++cts[32 * w + (static_cast<uint32_t>(__builtin_ctzll(miss)) >> 1)];
+        miss &= miss - 1;
+      }
+    }
+  }
+}
+
+uint32_t mind_decide(const Session& S, const std::vector<uint32_t>& missing_cts, std::vector<uint8_t>* removed) {
+  const Args& A = S.A;
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  // a sample goes when it misses more than (int32_t)(variant_ct * (thresh * (1 + 2^-44))) calls (MindFilter :3340-3342; no chrY here)
+  const double thresh = A.mind * (1 + kSmallEpsilon);
+  const uint32_t max_missing = static_cast<uint32_t>(static_cast<int32_t>(static_cast<double>(S.mind_variant_ct) * thresh));
+  removed->assign(raw_sample_ct, 0);
+  uint32_t removed_ct = 0;
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    if ((S.sample_kept.empty() || S.sample_kept[sx]) && (missing_cts[sx] > max_missing)) {
+      (*removed)[sx] = 1;
+      ++removed_ct;
+    }
+  }
+  logprintf("%u sample%s removed due to missing genotype data (--mind).\n", removed_ct, (removed_ct == 1) ? "" : "s");
+  if (removed_ct) {
+    // WriteSampleIds, plink2_common.cc:4219-4270
+    const std::string path = A.out + ".mindrem.id";
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) {
+      die(3, "Error: Failed to open %s for writing.\n", path.c_str());
+    }
+    fputs(S.fid_present ? "#FID\tIID" : "#IID", f);
+    fputs(S.sample_sids.empty() ? "\n" : "\tSID\n", f);
+    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+      if ((*removed)[sx]) {
+        fputs(S.sample_keys[sx].c_str() + (S.fid_present ? 0 : 2), f);  // (no FID column: every key starts with "0<tab>")
+        if (!S.sample_sids.empty()) {
+          fputc('\t', f);
+          fputs(S.sample_sids[sx].c_str(), f);
+        }
+        fputc('\n', f);
+      }
+    }
+    if (fclose(f)) {
+      die(5, "Error: File write failure: %s.\n", path.c_str());
+    }
+    logprintf("ID%s written to %s .\n", (removed_ct == 1) ? "" : "s", path.c_str());
+  }
+  return removed_ct;
+}
+
+void mind_apply(Session& S, const std::vector<uint8_t>& removed) {
+  if (S.sample_kept.empty()) {
+    S.sample_kept.assign(S.is_founder.size(), 1);
+  }
+  bool any = false;
+  for (size_t sx = 0; sx < removed.size(); ++sx) {
+    if (removed[sx]) {
+      S.sample_kept[sx] = 0;
+      S.is_founder[sx] = 0;
+    }
+    any = any || S.sample_kept[sx];
+  }
+  if (!any) {  // plink2.cc:1836-1838
+    die(13, "Error: No samples remaining after main filters.\n");
+  }
+}
+
+// The --mind stage of load_inputs(): the variants the table filters leave (--chr / --not-chr / --autosome, --extract / --exclude, --snps-only,
+// --max-alleles; chromosome 0 and multiallelic variants count, everything before --geno does), then one of
+//   * a restarted run: the first run's decision, applied as --remove would have;
+//   * the decision left to run_prune() (S.mind_device), which reads the counts off the resident image;
+//   * the host pass: a multi-threaded pass over the rows like the one --geno has -- fixed-width rows where they lie, variable-width records through
+//     ldp_pgen_read, .bed codes -- that counts the missing hardcalls of every kept sample (a dosage track changes no hardcall), then the decision.
+static void sample_filter_mind(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
+  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome
+  std::vector<uint32_t> todo;
+  bool any_x_mt = false, any_multiallelic = false;
+  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
+    auto it = chr_state.find(V.chrom[v]);
+    if (it == chr_state.end()) {
+      const std::string& cur = V.chrom[v];
+      const int code = chrom_code(cur);
+      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
+                                       (A.autosome && !((code >= 1) && (code <= 22))));
+      bool zero = false;
+      const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
+      if (!out) {
+        if (cls == 2) {
+          die(6, "Error: Invalid chromosome code '%s'. (Use --allow-extra-chr to force it to be accepted.)\n", cur.c_str());
+        }
+        if (cls == 4) {
+          // (the reference counts chrY over the males only and gives the others a smaller denominator, MindFilter :3341-3355: not built)
+          die(63, "Error: --mind with chrY variants ('%s') is not supported by plink2-hip: filter them out (--autosome, --not-chr y) or pre-filter with plink2.\n", cur.c_str());
+        }
+        any_x_mt = any_x_mt || (cls == 3) || (cls == 5);
+      }
+      it = chr_state.emplace(cur, static_cast<uint8_t>(out)).first;
+    }
+    if (it->second || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
+      continue;
+    }
+    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
+      continue;
+    }
+    any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
+    todo.push_back(v);
+  }
+  S.mind_variant_ct = static_cast<uint32_t>(todo.size());
+  if (S.mind_decided) {
+    mind_apply(S, S.mind_removed);
+    uint32_t kept = 0, founders = 0;
+    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+      kept += S.sample_kept[sx];
+      founders += S.is_founder[sx];
+    }
+    g_log_mute = false;
+    logprintf("--mind: %u sample%s remaining (%u founder%s); the rows are loaded again without the removed samples.\n", kept, (kept == 1) ? "" : "s", founders,
+              (founders == 1) ? "" : "s");
+    g_log_mute = true;
+    return;
+  }
+  int storage_mode = 0;
+  ldp_pgen_info(S.pg, nullptr, nullptr, &storage_mode, nullptr, nullptr);
+  uint32_t kept_samples = 0, founders = 0;
+  const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
+  std::vector<uint64_t> m_s(words, 0);
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    if (S.sample_kept.empty() || S.sample_kept[sx]) {
+      m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
+      ++kept_samples;
+    }
+    founders += S.is_founder[sx];
+  }
+  // from the resident image where the variant filters may come from the device's records, and where in addition the image's rows ARE the
+  // hardcalls of the variants counted and its columns the final founders
+  const char* reason = device_filter_refusal(A, ldp_pgen_has_dosage(S.pg) != 0, kept_samples, founders);
+  if (!reason) {
+    reason = A.dry_run ? "--dry-run"
+             : ((A.make_founders && !A.make_founders_first) ? "--make-founders runs after --mind, on the samples it leaves"
+             : (any_x_mt ? "chrX / MT variants (their rows are built for engines of their own)"
+             : (any_multiallelic ? "multiallelic variants (their rows are collapsed on the way into the image)" : nullptr)));
+  }
+  if (A.dry_run) {
+    logprintf("dry-run: sample filter (--mind): host pass over %u variant%s\n", S.mind_variant_ct, (S.mind_variant_ct == 1) ? "" : "s");
+  }
+  if (!reason) {
+    S.mind_device = true;
+    return;
+  }
+  const double t0 = now_s();
+  const bool bed = (storage_mode == 0x01);
+  uint64_t rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
+  const uint8_t* direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(S.pg, &rec_bytes));  // NULL for variable-width
+  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  std::vector<std::vector<uint32_t>> part(nthreads, std::vector<uint32_t>(32 * words, 0));  // (per thread; summed below)
+  for_each_row_run(S.pg, S.gpath, direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t) {
+    count_sample_missing(rows, rec_bytes, n, bed, raw_sample_ct, m_s, part[t].data());
+  });
+  std::vector<uint32_t> missing_cts(raw_sample_ct, 0);
+  for (const std::vector<uint32_t>& p : part) {
+    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+      missing_cts[sx] += p[sx];
+    }
+  }
+  std::vector<uint8_t> removed;
+  if (mind_decide(S, missing_cts, &removed)) {
+    mind_apply(S, removed);
+  }
+  if (A.timing) {
+    logprintf("[timing] sample filter (--mind): host pass (%.3f s; %s)\n", now_s() - t0, reason);
+  }
+}
+
 void load_inputs(Session& S, int argc, char** argv) {
-  S.t_begin = now_s();
+  S.t_begin = S.t_begin_first ? S.t_begin_first : now_s();
   S.A = parse_args(argc, argv);
   const Args& A = S.A;
   const double t_begin = S.t_begin;
-  g_log = fopen((A.out + ".log").c_str(), "w");
+  if (!g_log) {
+    g_log = fopen((A.out + ".log").c_str(), "w");
+  }
+  // (a run that --mind started over: this load's lines were logged by the first one, up to the one line below that says what changed)
+  g_log_mute = S.mind_decided;
   logprintf("plink2-hip: MI355X-native --indep-pairwise (drop-in for that path of PLINK v2.0)\n");
   logprintf("Options in effect:\n ");
   for (int i = 1; i < argc; ++i) {
@@ -257,12 +503,17 @@ void load_inputs(Session& S, int argc, char** argv) {
   Variants& V = S.V;
   std::thread t_variants([&]() { load_variants(A, &V); });
   // (the HIP runtime start-up AND the context of device 0 -- its queues, the first pinned allocation -- beside the table parsing)
-  S.t_hip = std::thread([&S]() { const double t0 = now_s(); if (ldp_device_count() > 0) { (void)ldp_prewarm(0); } S.t_hip_init = now_s() - t0; });
+  S.t_joined = now_s();   // (a restarted run: the runtime is up, there is nothing to start or to join)
+  if (!S.mind_decided) {
+    S.t_hip = std::thread([&S]() { const double t0 = now_s(); if (ldp_device_count() > 0) { (void)ldp_prewarm(0); } S.t_hip_init = now_s() - t0; });
+  }
   std::vector<uint8_t>& is_founder = S.is_founder;
-  std::vector<std::string> sample_keys;
+  std::vector<std::string>& sample_keys = S.sample_keys;
   const bool sample_filter = (!A.keep_files.empty()) || (!A.remove_files.empty());
+  const bool mind_on = (A.mind < 1.0);  // plink2.cc:8910
   std::vector<std::pair<std::string, std::string>> parent_keys;
-  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr);
+  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
+               &S.sample_sids);
   // --make-founders (MakeFounders, plink2_filter.cc:4372-4443): a non-founder with a parent (both, with 'require-2-missing') that
   // is not among the samples in play becomes a founder; 'first' applies it before --keep / --remove, else after them
   auto make_founders = [&](const std::vector<uint8_t>* included) {
@@ -330,10 +581,51 @@ void load_inputs(Session& S, int argc, char** argv) {
       die(13, "Error: No samples remaining after main filters.\n");
     }
   }
+  // ---- what --mind needs earlier than the other filters, and they where they always were: the genotype file (.bed / fixed-width .pgen / standard
+  // variable-width .pgen) and the --extract / --exclude ID sets
+  ldp_pgen*& pg = S.pg;
+  auto open_genotypes = [&]() {
+    if (pg) {
+      return;
+    }
+    S.is_bed = !A.bed.empty();
+    S.gpath = S.is_bed ? A.bed : A.pgen;
+    if (ldp_pgen_open_indexed(S.gpath.c_str(), A.pgi.empty() ? nullptr : A.pgi.c_str(), static_cast<uint32_t>(is_founder.size()), static_cast<uint32_t>(V.id.size()), &pg)) {
+      die(6, "Error: %s: %s\n", S.gpath.c_str(), ldp_pgen_last_error(pg));
+    }
+  };
+  std::unordered_set<std::string> extract_ids, exclude_ids;
+  bool id_sets_loaded = false;
+  auto load_id_sets = [&]() {
+    if (id_sets_loaded) {
+      return;
+    }
+    id_sets_loaded = true;
+    for (const std::string& fn : A.extract_files) {
+      for (std::string& t : tokens_of_file(fn)) {
+        extract_ids.insert(std::move(t));
+      }
+    }
+    for (const std::string& fn : A.exclude_files) {
+      for (std::string& t : tokens_of_file(fn)) {
+        exclude_ids.insert(std::move(t));
+      }
+    }
+  };
+  const bool chr_filter = (!A.chr_keep.empty()) || (!A.chr_drop.empty()) || A.autosome;
+  // ---- --mind: after --keep / --remove, before --make-founders (unless 'first'), --geno and the founder count (plink2.cc:1600-1840)
+  if (mind_on) {
+    t_variants.join();
+    open_genotypes();
+    load_id_sets();
+    sample_filter_mind(S, chr_filter, extract_ids, exclude_ids);
+  }
   if (A.make_founders && !A.make_founders_first) {
     make_founders(S.sample_kept.empty() ? nullptr : &S.sample_kept);
   }
-  t_variants.join();
+  if (t_variants.joinable()) {
+    t_variants.join();
+  }
   S.t_parse = now_s() - t_begin;
   S.raw_sample_ct = static_cast<uint32_t>(is_founder.size());
   const uint32_t raw_sample_ct = S.raw_sample_ct;
@@ -357,14 +649,8 @@ void load_inputs(Session& S, int argc, char** argv) {
     die(7, "Error: %s requires at least two founders. (--make-founders may come in handy here.)\n", A.have_prune ? (A.pairphase ? "--indep-pairphase" : "--indep-pairwise") : "--r2-unphased");
   }
 
-  // ---- genotype file (.bed / fixed-width .pgen / standard variable-width .pgen)
-  S.is_bed = !A.bed.empty();
-  S.gpath = S.is_bed ? A.bed : A.pgen;
+  open_genotypes();
   const std::string& gpath = S.gpath;
-  ldp_pgen*& pg = S.pg;
-  if (ldp_pgen_open_indexed(gpath.c_str(), A.pgi.empty() ? nullptr : A.pgi.c_str(), raw_sample_ct, raw_variant_ct, &pg)) {
-    die(6, "Error: %s: %s\n", gpath.c_str(), ldp_pgen_last_error(pg));
-  }
   ldp_pgen_info(pg, nullptr, nullptr, &S.storage_mode, &S.encoding, &S.has_multiallelic);
   S.has_dosage = ldp_pgen_has_dosage(pg) != 0;
   if (S.has_dosage) {
@@ -390,18 +676,7 @@ void load_inputs(Session& S, int argc, char** argv) {
   uint32_t skipped = 0;
   // variant filters: --chr / --not-chr / --autosome by chromosome, then --extract, then --exclude by ID
   // (TokenExtractExclude, plink2_filter.cc:367: every variant carrying a listed ID, unknown IDs ignored)
-  std::unordered_set<std::string> extract_ids, exclude_ids;
-  for (const std::string& fn : A.extract_files) {
-    for (std::string& t : tokens_of_file(fn)) {
-      extract_ids.insert(std::move(t));
-    }
-  }
-  for (const std::string& fn : A.exclude_files) {
-    for (std::string& t : tokens_of_file(fn)) {
-      exclude_ids.insert(std::move(t));
-    }
-  }
-  const bool chr_filter = (!A.chr_keep.empty()) || (!A.chr_drop.empty()) || A.autosome;
+  load_id_sets();
   uint32_t after_extract = 0, after_exclude = 0;
   // --geno / --maf / --max-maf need genotype counts before the variant list is final: one multi-threaded pass over the rows of
   // the variants the table filters leave (host popcounts; the rows are read again when they go to the device)
@@ -473,52 +748,9 @@ void load_inputs(Session& S, int argc, char** argv) {
       std::vector<RowCounts> counts(todo.size());
       const bool bed = (S.storage_mode == 0x01);
       const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-      if (S.direct_rows) {
-        std::atomic<size_t> next(0);
-        const size_t kTask = 2048;
-        std::vector<std::thread> pool;
-        for (uint32_t t = 0; t < nthreads; ++t) {
-          pool.emplace_back([&]() {
-            for (size_t q0 = next.fetch_add(kTask); q0 < todo.size(); q0 = next.fetch_add(kTask)) {
-              const size_t q1 = std::min(todo.size(), q0 + kTask);
-              for (size_t q = q0; q < q1; ++q) {
-                count_rows(S.direct_rows + static_cast<uint64_t>(todo[q]) * S.rec_bytes, S.rec_bytes, 1, bed, raw_sample_ct, m_f, m_s, &counts[q]);
-              }
-            }
-          });
-        }
-        for (std::thread& th : pool) {
-          th.join();
-        }
-      } else {
-        // variable-width records: decode runs of file-consecutive variants (all host threads), then count them
-        const uint32_t max_run = std::max<uint32_t>(1, static_cast<uint32_t>((256ull << 20) / std::max<uint64_t>(S.rec_bytes, 1)));
-        std::vector<uint8_t> decoded;
-        for (size_t q0 = 0; q0 < todo.size();) {
-          uint32_t run = 1;
-          while ((q0 + run < todo.size()) && (todo[q0 + run] == todo[q0] + run) && (run < max_run)) {
-            ++run;
-          }
-          decoded.resize(static_cast<size_t>(run) * S.rec_bytes);
-          if (ldp_pgen_read(pg, todo[q0], run, decoded.data(), S.rec_bytes, 0)) {
-            die(6, "Error: %s: %s\n", gpath.c_str(), ldp_pgen_last_error(pg));
-          }
-          std::atomic<uint32_t> next(0);
-          std::vector<std::thread> pool;
-          for (uint32_t t = 0; t < nthreads; ++t) {
-            pool.emplace_back([&]() {
-              for (uint32_t r0 = next.fetch_add(256); r0 < run; r0 = next.fetch_add(256)) {
-                const uint32_t n = std::min(256u, run - r0);
-                count_rows(decoded.data() + static_cast<uint64_t>(r0) * S.rec_bytes, S.rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &counts[q0 + r0]);
-              }
-            });
-          }
-          for (std::thread& th : pool) {
-            th.join();
-          }
-          q0 += run;
-        }
-      }
+      for_each_row_run(pg, gpath, S.direct_rows, S.rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
+        count_rows(rows, S.rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &counts[q]);
+      });
       if (S.has_dosage && freq_filter) {
         std::vector<uint32_t> with_track;
         for (uint32_t v : todo) {
@@ -544,6 +776,12 @@ void load_inputs(Session& S, int argc, char** argv) {
         logprintf("[timing] variant filters: host pass (%.3f s; %s)\n", S.host_filter_s, S.host_filter_reason ? S.host_filter_reason : "--dry-run");
       }
     }
+  }
+  if (S.mind_device && !S.device_filter) {
+    // (no count filter, or none that reached the block above: the rows --mind counts over are loaded under the all-pairs plan all the same, chromosome 0
+    // included, and run_prune() plans over what is left once the samples are decided)
+    S.device_filter = true;
+    S.kept_sample_ct = founder_ct;
   }
   {
     std::unordered_set<std::string> seen_chr;
@@ -680,6 +918,7 @@ void load_inputs(Session& S, int argc, char** argv) {
     m_chr[q] = chr_idx[mk[q]];
     m_bps[q] = bps[mk[q]];
   }
+  g_log_mute = false;
 }
 
 

@@ -725,6 +725,43 @@ struct PruneJob {
     }
   }
 
+  // --mind from the resident image (Session::mind_device): every row the table filters leave is loaded -- chromosome 0 included, under the all-pairs
+  // plan --, ldp_sample_missing_counts() reads the image once in the sample direction, and MindFilter's rule (mind_decide, the one the host pass
+  // uses) decides.  Nobody goes: false, and the run goes on with the image it has.  Somebody goes: the image's columns cannot be dropped in place,
+  // so the engine is destroyed and true tells run() to hand the decision back to main(), which starts over with those samples excluded.
+  bool mind_on_device() {
+    if (m_ct != S.mind_variant_ct) {
+      die(16, "\nError: internal: --mind counted %u variants on the host's list and %u rows are loaded.\n", S.mind_variant_ct, m_ct);
+    }
+    std::vector<uint32_t> by_column(std::max<uint32_t>(founder_ct, 1), 0);
+    if (ldp_sample_missing_counts(eng[0], 0, m_ct, by_column.data())) {
+      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+    }
+    std::vector<uint32_t> missing_cts(raw_sample_ct, 0);
+    for (uint32_t f = 0; f < founder_ct; ++f) {
+      missing_cts[founder_idx[f]] = by_column[f];  // (column f of the image is founder f of the file: every kept sample is a founder here)
+    }
+    std::vector<uint8_t> removed_samples;
+    const uint32_t removed_ct = mind_decide(S, missing_cts, &removed_samples);
+    if (A.timing) {
+      double ms = 0.0;
+      uint64_t bytes = 0;
+      (void)ldp_debug_get_sample_missing_stats(eng[0], &ms, &bytes);
+      logprintf("[timing] sample filter (--mind): from the resident image (%u rows, %.3f ms = %.0f GB/s; %u sample%s removed%s)\n", m_ct, ms,
+                (ms > 0.0) ? (static_cast<double>(bytes) / 1e9 / (ms * 1e-3)) : 0.0, removed_ct, (removed_ct == 1) ? "" : "s", removed_ct ? ", reloading" : "");
+    }
+    if (!removed_ct) {
+      return false;
+    }
+    mind_apply(S, removed_samples);  // (exit 13 when nobody is left)
+    ldp_destroy(eng[0]);
+    eng.clear();
+    S.file_to_hbm_done();
+    S.mind_removed = removed_samples;
+    S.restart = true;
+    return true;
+  }
+
   // --geno / --maf / --max-maf / --mac / --max-mac from the records the load's own count pass left on the device (nm_ct and the three
   // genotype counts of every row, over the founders = the kept samples: device_filter_refusal): the arithmetic of the host's pass
   // (CountFilters), then the engine drops the variants that go and plans over the rest (ldp_restrict_variants), and the session's variant
@@ -795,7 +832,7 @@ struct PruneJob {
   }
 
   void report_filter_timing() {
-    if (!A.timing) {
+    if ((!A.timing) || !S.count_filters) {  // (--mind alone takes this path too: no variant filter to report)
       return;
     }
     logprintf("[timing] variant filters: from the device's count pass (%llu rows compacted, %.3f ms; records, filter arithmetic and the new plan %.3f s in all)\n",
@@ -1163,6 +1200,9 @@ struct PruneJob {
       t_load0 = now_s();
       set_row_geometry();
       load_diploid_rows();
+      if (S.mind_device && mind_on_device()) {
+        return 0;  // (S.restart: main() starts over without the removed samples)
+      }
       filter_on_device();
       check_unique_ids();
     }

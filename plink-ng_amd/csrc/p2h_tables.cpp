@@ -6,7 +6,7 @@ namespace p2h {
 // founder <=> PAT and MAT are both exactly "0" (plink2_psam.cc:804-806); absent columns => founder
 // sex: 1 = male, 2 = female, anything else = unknown (plink2_psam.cc:808-813)
 void load_samples(const Args& A, std::vector<uint8_t>* is_founder, std::vector<uint8_t>* sex, std::vector<std::string>* fid_iid,
-                  std::vector<std::pair<std::string, std::string>>* parents) {
+                  std::vector<std::pair<std::string, std::string>>* parents, bool* fid_present, std::vector<std::string>* sids) {
   const bool psam = !A.psam.empty();
   const std::string& path = psam ? A.psam : A.fam;
   std::ifstream in(path);
@@ -14,8 +14,11 @@ void load_samples(const Args& A, std::vector<uint8_t>* is_founder, std::vector<u
     die(3, "Error: Failed to open %s.\n", path.c_str());
   }
   std::string line;
-  int pat_col = -1, mat_col = -1, sex_col = -1, iid_col = 0;
+  int pat_col = -1, mat_col = -1, sex_col = -1, iid_col = 0, sid_col = -1;
   bool header_seen = false, has_fid = false;
+  if (fid_present) {
+    *fid_present = true;  // (.fam, and a .psam without a header line: FID IID ...)
+  }
   while (std::getline(in, line)) {
     if (line.empty()) {
       continue;
@@ -31,6 +34,12 @@ void load_samples(const Args& A, std::vector<uint8_t>* is_founder, std::vector<u
         has_fid = (cols[0] == "#FID");
         iid_col = has_fid ? 1 : 0;
         header_seen = true;
+        if ((cols.size() > static_cast<size_t>(iid_col + 1)) && (cols[iid_col + 1] == "SID")) {
+          sid_col = iid_col + 1;
+        }
+        if (fid_present) {
+          *fid_present = has_fid;
+        }
       }
       continue;
     }
@@ -70,6 +79,12 @@ void load_samples(const Args& A, std::vector<uint8_t>* is_founder, std::vector<u
           die(6, "Error: Fewer tokens than expected in %s.\n", path.c_str());
         }
         fid_iid->push_back((has_fid ? t[0] : std::string("0")) + "\t" + t[iid_col]);
+      }
+      if (sids && (sid_col >= 0)) {
+        if (static_cast<size_t>(sid_col) >= t.size()) {
+          die(6, "Error: Fewer tokens than expected in %s.\n", path.c_str());
+        }
+        sids->push_back(t[sid_col]);
       }
       uint8_t sx = 0;
       if (sex_col >= 0 && static_cast<size_t>(sex_col) < t.size()) {

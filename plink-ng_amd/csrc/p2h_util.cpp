@@ -7,6 +7,7 @@ namespace p2h {
 
 
 FILE* g_log = nullptr;
+bool g_log_mute = false;    // the second load_inputs() of a run that --mind restarted: what it would log was logged by the first
 bool g_silent = false;       // --silent: the log file still gets every line, the terminal only errors
 bool g_r_unsquared = false;  // --r-unphased: the messages below name that flag where they say --r2-unphased
 
@@ -27,6 +28,9 @@ double now_s() {
 }
 
 void logprintf(const char* fmt, ...) {
+  if (g_log_mute) {
+    return;
+  }
   char buf[4096];
   va_list ap;
   va_start(ap, fmt);

@@ -15,7 +15,8 @@
 // their sample-mapped rows (males het->missing, non-males x2, ...) built on the host as well.
 // --r2-unphased / --r-unphased: the matrix shapes (square/square0/triangle as bin, bin4 or text, zs), the windowed and the
 // inter-chr .vcor table with cols=, --ld-window, --ld-window-kb, --ld-window-cm, --ld-window-r2, --ld-snp / --ld-snps / --ld-snp-list,
-// --parallel; number formatting restated from dtoa_g.  --clump (several reports, --clump-allow-overlap, cols=, bins, -log10,
+// --parallel; number formatting restated from dtoa_g.  --mind for every command: per-sample missing-call counts from the resident image where the job
+// allows it (ldp_sample_missing_counts; samples that go make the run start over without them, in this process), from a host pass otherwise.  --clump (several reports, --clump-allow-overlap, cols=, bins, -log10,
 // ranges, sex chromosomes, (variant, A1 allele) pairs of multiallelic sites).
 // Not yet supported (reported as such with exit 63, never silently mis-handled): dosage data outside --indep-pairwise on the autosomes,
 // more than 254 ALT alleles (multiallelic sites on chrX/Y/MT are taken by every command since round 5), major-allele-oriented
@@ -64,7 +65,24 @@ int main(int argc, char** argv) {
   if ((argc == 3) && (strcmp(argv[1], "--debug-xweighted") == 0)) {
     return debug_xweighted(argv[2]);
   }
-  Session S;
-  load_inputs(S, argc, argv);
-  return S.A.have_r2 ? run_r2(S) : run_prune(S);
+  // One pass, or two: a --mind that was decided from the resident image and removed samples ends run_prune() early (Session::restart); the run
+  // then starts over in this process -- no exec: the GPU is initialised -- with the decision made and those samples excluded as --remove would.
+  std::vector<uint8_t> mind_removed;
+  double t_first = 0.0;
+  for (bool again = false;; again = true) {
+    Session S;
+    S.mind_decided = again;
+    S.mind_removed = mind_removed;
+    S.t_begin_first = t_first;
+    load_inputs(S, argc, argv);
+    const int rc = S.A.have_r2 ? run_r2(S) : run_prune(S);
+    if (!S.restart) {
+      return rc;
+    }
+    mind_removed = S.mind_removed;
+    t_first = S.t_begin;
+    if (S.pg) {
+      ldp_pgen_close(S.pg);
+    }
+  }
 }

@@ -44,7 +44,7 @@ def run(binary, cwd, pfile, filters, kb, r2, out, extra=(), runs=2, timeout_s=15
         walls.append(wall)
     lines = txt.splitlines()
     return {"rc": rc, "wall_s": min(walls) if walls else None, "wall_s_runs": walls,
-            "variant_filters_line": [ln for ln in lines if ("variant filters:" in ln) or ("[timing] compaction:" in ln)],
+            "variant_filters_line": [ln for ln in lines if ("variant filters:" in ln) or ("[timing] compaction:" in ln) or ("sample filter (--mind):" in ln)],
             "filter_log_lines": [ln.strip() for ln in lines if "removed due to" in ln],
             "removed_line": [ln.strip() for ln in lines if re.search(r"\d+/\d+ variants removed", ln)][-1:],
             "timing_lines": [ln for ln in lines if ln.startswith("[timing]")][:12], "tail": txt[-400:] if rc else ""}
