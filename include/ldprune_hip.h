@@ -260,7 +260,10 @@ int ldp_map_rows(ldp_engine* e, uint32_t first_variant, uint32_t n, void** devic
  * ReadGenovecSubsetUnsafe, pgenlib_read.cc:2849-2912: plain 2-bit, one-bit + exceptions, difflists, LD-compressed chains,
  * pgenlib_read.cc:2186-2760; and for variants with more than one ALT allele Get1Multiallelic, pgenlib_read.cc:5417-5563, with
  * the major allele chosen as ComputeAlleleFreqs / GetMajIdxMulti do, plink2_filter.cc:2113-2153, plink2_common.cc:1042-1070).
- * Only the main track and auxiliary track 1 are read; phase and dosage tracks behind them are ignored.
+ * The rows come from the main track and auxiliary track 1; a phase track behind them is skipped.  A DOSAGE track (type byte bits 5-6) of a
+ * record with one ALT allele is summed on the way, where the record's bytes and its decoded row lie side by side: the two allele dosage
+ * sums of the engine's samples (ldp_get_dosage_sums), from which the reference takes such a variant's allele frequencies
+ * (plink2_data.cc:2421-2443).  The rows stay the hardcalls.
  *   recs[q]      record of variant first_variant + q inside `bytes` (host or device memory, `location`): offset, length, the
  *                file's variant record type byte, and the allele count from the .pvar (ldp_pgen_record_index() fills the first
  *                three from a file's index).  Variants this engine does not own are decoded too (LD chains run through them).
@@ -289,6 +292,15 @@ typedef struct ldp_pgen_rec {
 } ldp_pgen_rec;
 int ldp_load_pgen_records(ldp_engine* e, uint32_t first_variant, uint32_t n, const void* bytes, uint64_t n_bytes, int location, const ldp_pgen_rec* recs,
                           const ldp_pgen_rec* ld_base, uint32_t raw_sample_ct, uint32_t* major_allele_out);
+/* The allele dosage sums that ldp_load_pgen_records() computed on the device for variants [first_variant, +n) (the engine's current
+ * indices): has_sums[q] = 1 when the row of variant first_variant + q was loaded by that call from a record with one ALT allele and a
+ * dosage track, over the file's samples or a sample map that is a plain subset of them, on an engine that keeps 2-bit codes;
+ * ref_dosage[q] / alt_dosage[q] are then exactly what ldp_pgen_dosage_sums() gives for the same record over the same samples.
+ * has_sums[q] = 0 (and zero sums) otherwise: no dosage track, several ALT alleles, a variant this engine does not own, a row loaded by
+ * any other call -- a later load of a row replaces its entry --, ldp_load_pgen_records_phased(), a map that is no plain subset.  The
+ * entries follow their rows through ldp_restrict_variants(); ldp_set_variants*() and ldp_release_device() clear them.  No device work:
+ * the sums came back with the load's own synchronisation.  LDP_ERR_INVALID for a range beyond variant_ct. */
+int ldp_get_dosage_sums(ldp_engine* e, uint32_t first_variant, uint32_t n, uint64_t* ref_dosage, uint64_t* alt_dosage, uint8_t* has_sums);
 /* The same for --indep-pairphase (plink2_ld.cc:1449-2163; loader :2040-2052): the records' main tracks AND their hardcall-phase tracks
  * (auxiliary track 2, pgen_spec "Phased heterozygous hard-calls"; ReadGenovecHphaseSubsetUnsafe pgenlib_read.cc:6704, what
  * PgrGetInv1P :7016 hands HapsplitMustPhased pgenlib_misc.cc:1887) are decoded on the device into LDP_GENO_PHASED rows and loaded;

@@ -113,6 +113,7 @@ CABI_SYMBOLS = [
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
+    "ldp_get_dosage_sums",
 ]
 
 
@@ -262,6 +263,7 @@ def lib():
     L.ldp_debug_mfma_plan.argtypes = [vp, u32p, u32p, ctypes.c_uint64, u32p, u32p]
     L.ldp_get_variant_recs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp]
     L.ldp_get_maj_freqs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, f64p]
+    L.ldp_get_dosage_sums.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p, ctypes.POINTER(ctypes.c_uint8)]
     L.ldp_get_planes.argtypes = [vp, ctypes.c_uint32, u32p, u32p]
     L.ldp_get_counters.argtypes = [vp, ctypes.POINTER(ldp_counters)]
     L.ldp_synth_genotypes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, vp,
@@ -1003,6 +1005,16 @@ class LdPruneEngine:
         out = np.zeros(max(n, 1), dtype=np.float64)
         self._ck(self._L.ldp_get_maj_freqs(self._h, first, n, _ptr(out, ctypes.c_double)))
         return out[:n]
+
+    def dosage_sums(self, first=0, n=None):
+        """(ref, alt, has): the allele dosage sums ldp_load_pgen_records() computed on the device for variants [first, first + n) -- uint64
+        arrays, what PgenFile.dosage_sums() gives over the engine's samples -- and has[q] = 1 where it did (ldp_get_dosage_sums)."""
+        n = self.variant_ct - first if n is None else n
+        ref = np.zeros(max(n, 1), dtype=np.uint64)
+        alt = np.zeros(max(n, 1), dtype=np.uint64)
+        has = np.zeros(max(n, 1), dtype=np.uint8)
+        self._ck(self._L.ldp_get_dosage_sums(self._h, first, n, _ptr(ref, ctypes.c_uint64), _ptr(alt, ctypes.c_uint64), _ptr(has, ctypes.c_uint8)))
+        return ref[:n], alt[:n], has[:n]
 
     def planes(self, variant):
         w = (self.founder_ct + 31) // 32

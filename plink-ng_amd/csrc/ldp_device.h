@@ -454,11 +454,17 @@ struct PgenDecodeArgs {
   uint64_t phase_off;           // byte offset of the phase bits inside a row (a multiple of 4, < stride)
   uint32_t* unphased;           // out: lowest record index with a het call that has no phase (atomicMin; preset to UINT32_MAX)
   int no_lds;                   // (test hook, option "decode_no_lds") assemble rows in global memory whatever their size
+  // records with one ALT allele and a dosage track: their two allele dosage sums over the samples of sample_mask (pgen_dosage_kernel)
+  const uint32_t* dosage_rec;   // record indices
+  uint32_t n_dosage;
+  uint64_t* dosage_sums;        // out, per entry of dosage_rec: (REF sum, ALT sum), what ldp_pgen_dosage_sums() gives
 };
 hipError_t launch_pgen_main(const PgenDecodeArgs& a, hipStream_t stream);
 // the phase tracks of records [0, n_records) on top of their decoded main tracks (after launch_pgen_main on the same stream)
 hipError_t launch_pgen_phase(const PgenDecodeArgs& a, uint32_t n_records, hipStream_t stream);
 hipError_t launch_pgen_aux1(const PgenDecodeArgs& a, hipStream_t stream);
+// the dosage sums of records dosage_rec[0 .. n_dosage): after launch_pgen_main on the same stream, before anything rewrites or gathers their rows
+hipError_t launch_pgen_dosage(const PgenDecodeArgs& a, hipStream_t stream);
 
 // Sample-mapped rows (ldp_set_sample_map): out row v = 2-bit REF codes of columns map[f] & 0x7fffffff of in row v, hets of
 // columns with bit 31 set replaced by missing and counted into extra_het[v]; in rows are .pgen- or .bed-coded.

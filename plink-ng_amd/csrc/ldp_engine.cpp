@@ -134,7 +134,7 @@ void free_device(ldp_engine* e, bool keep_image) {
   }
   e->ld_base_valid = false;
   if (!keep_image) {
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < ldp_engine::kDecSlots; ++k) {
       (void)hipFree(e->dec.ptr[k]);
       e->dec.ptr[k] = nullptr;
       e->dec.cap[k] = 0;
@@ -938,6 +938,9 @@ void build_shard(ldp_engine* e) {
   e->maj_freq.assign(local, 0.0);
   e->mf_set.assign(local, 0);
   e->row_inv_loaded.assign(local, 0);
+  e->dos_ref.assign(local, 0);
+  e->dos_alt.assign(local, 0);
+  e->dos_has.assign(local, 0);
   e->loaded_special = false;
 }
 
@@ -1564,6 +1567,7 @@ int ldp_release_device(ldp_engine* e) {
   // the rows are gone with the image: everything has to be loaded again before the next run
   std::fill(e->loaded.begin(), e->loaded.end(), 0);
   std::fill(e->load_tag.begin(), e->load_tag.end(), 0);
+  std::fill(e->dos_has.begin(), e->dos_has.end(), 0);
   for (uint8_t& m : e->mf_set) {
     m = (m == 1) ? 1 : 0;  // (caller-supplied frequencies stay)
   }
@@ -1894,6 +1898,23 @@ int ldp_get_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, double*
   for (uint32_t q = 0; q < n; ++q) {
     const int64_t l = e->global_to_local[first_variant + q];
     out[q] = ((l >= 0) && e->mf_set[l]) ? e->maj_freq[l] : 0.0;
+  }
+  return LDP_OK;
+}
+
+int ldp_get_dosage_sums(ldp_engine* e, uint32_t first_variant, uint32_t n, uint64_t* ref_dosage, uint64_t* alt_dosage, uint8_t* has_sums) {
+  if (!e || !e->planned) {
+    return e ? fail(e, LDP_ERR_STATE, "ldp_set_variants() first") : LDP_ERR_INVALID;
+  }
+  if ((static_cast<uint64_t>(first_variant) + n > e->variant_ct) || (n && (!ref_dosage || !alt_dosage || !has_sums))) {
+    return fail(e, LDP_ERR_INVALID, "variant range out of bounds / null output pointer");
+  }
+  for (uint32_t q = 0; q < n; ++q) {
+    const int64_t l = e->global_to_local[first_variant + q];
+    const bool has = (l >= 0) && e->loaded[l] && e->dos_has[l];
+    has_sums[q] = has ? 1 : 0;
+    ref_dosage[q] = has ? e->dos_ref[l] : 0;
+    alt_dosage[q] = has ? e->dos_alt[l] : 0;
   }
   return LDP_OK;
 }

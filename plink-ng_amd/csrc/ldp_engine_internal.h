@@ -302,6 +302,9 @@ struct ldp_engine {
   std::vector<uint8_t> mf_set;            // local: 0 unset, 1 caller-supplied, 2 to be derived from device counts, 3 derived
   std::vector<uint64_t> preferred;        // global bitmap (may be empty)
   std::vector<uint8_t> row_inv_loaded;    // local: the row was loaded as LDP_GENO_INVERSE (the call's encoding, or a collapsed multiallelic record)
+  // the allele dosage sums the device computed while it decoded a row's record (pgen_dosage_kernel; ldp_get_dosage_sums)
+  std::vector<uint64_t> dos_ref, dos_alt;  // local
+  std::vector<uint8_t> dos_has;            // local: 1 = the two above are set for the row as it is loaded now
   bool loaded_special = false;            // some row came as LDP_GENO_PHASED or through a sample map that is no plain subset: a count of the image row alone
                                           // would not give its record again (ldp_restrict_variants refuses such engines)
 
@@ -384,9 +387,10 @@ struct ldp_engine {
   size_t extra_het_cap = 0;
   // ldp_load_pgen_records(): device scratch of one launch (bytes, record descriptors, decoded rows, per-record outputs) and the
   // most recent non-LD row, kept for a call that continues where this one stopped
+  static constexpr int kDecSlots = 10;
   struct DecodeScratch {
-    void* ptr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void* ptr[kDecSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t cap[kDecSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   } dec;
   uint8_t* h_dec_pin = nullptr;  // pinned: the launch's descriptors going up, its per-record results coming down (pageable copies cost ~0.2 ms each)
   size_t dec_pin_cap = 0;

@@ -303,6 +303,7 @@ int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void
       }
       std::fill(e->loaded.begin() + l0, e->loaded.begin() + l0 + cnt, static_cast<uint8_t>(1));
       std::fill(e->load_tag.begin() + l0, e->load_tag.begin() + l0 + cnt, e->load_epoch);
+      std::fill(e->dos_has.begin() + l0, e->dos_has.begin() + l0 + cnt, static_cast<uint8_t>(0));  // (ldp_load_pgen_records sets them again behind this call)
       // (what ldp_restrict_variants() needs to count the rows again where they lie)
       if (!h_row_inverse) {
         std::fill(e->row_inv_loaded.begin() + l0, e->row_inv_loaded.begin() + l0 + cnt, static_cast<uint8_t>(base_encoding == LDP_GENO_INVERSE));
@@ -486,12 +487,16 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     rows_per_launch = e->opt.decode_rows;
   }
   std::vector<uint32_t> multi;
+  // Records with one ALT allele and a dosage track: their allele dosage sums are computed where the bytes and the decoded row lie side by
+  // side (pgen_dosage_kernel).  Over the file's samples or a plain subset of them; not for LDP_GENO_PHASED rows, not on bit-plane engines.
+  const bool want_sums = (!phased) && e->codes_format && ((!mapped) || e->map_is_subset);
+  std::vector<uint32_t> dos;
   std::vector<uint8_t> h_inverse;
   int status = LDP_OK;
-  // pinned staging for one launch: descriptors | multiallelic record indices | major-allele frequencies | major alleles | error word
+  // pinned staging for one launch: descriptors | major-allele frequencies | dosage sums | multiallelic record indices | major alleles | dosage record indices | error word
   {
     const size_t rows_max = static_cast<size_t>(rows_per_launch) + 1;
-    const size_t want = rows_max * (sizeof(ldp::PgenRecDesc) + sizeof(uint32_t) + sizeof(double) + sizeof(uint32_t)) + 64;  // (+ the error word and the unphased record behind them)
+    const size_t want = rows_max * (sizeof(ldp::PgenRecDesc) + sizeof(uint32_t) + sizeof(double) + sizeof(uint32_t) + 2 * sizeof(uint64_t) + sizeof(uint32_t)) + 64;  // (+ the error word and the unphased record behind them)
     if (e->dec_pin_cap < want) {
       HIP_TRY(e, hipStreamSynchronize(e->stream));
       if (e->h_dec_pin) {
@@ -506,9 +511,11 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
   const size_t rows_cap = static_cast<size_t>(rows_per_launch) + 1;
   ldp::PgenRecDesc* descs = reinterpret_cast<ldp::PgenRecDesc*>(e->h_dec_pin);
   double* h_maj_freq = reinterpret_cast<double*>(e->h_dec_pin + rows_cap * sizeof(ldp::PgenRecDesc));
-  uint32_t* h_multi = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(h_maj_freq) + rows_cap * sizeof(double));
+  uint64_t* h_sums = reinterpret_cast<uint64_t*>(h_maj_freq + rows_cap);
+  uint32_t* h_multi = reinterpret_cast<uint32_t*>(h_sums + 2 * rows_cap);
   uint32_t* h_maj_idx = h_multi + rows_cap;
-  int* h_err_pin = reinterpret_cast<int*>(h_maj_idx + rows_cap);
+  uint32_t* h_dos = h_maj_idx + rows_cap;
+  int* h_err_pin = reinterpret_cast<int*>(h_dos + rows_cap);
   for (uint32_t q0 = 0; (q0 < n) && (status == LDP_OK); q0 += rows_per_launch) {
     const double t_call = now_ms();
     const uint32_t cnt = std::min(rows_per_launch, n - q0);
@@ -518,6 +525,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       descs[q] = ldp::PgenRecDesc();
     }
     multi.clear();
+    dos.clear();
     uint32_t last_alone = with_base_rec ? cnt : (have_carried ? kPgenBaseCarried : kPgenNoBase);
     int64_t last_alone_row = -1;
     for (uint32_t q = 0; q < cnt; ++q) {
@@ -540,6 +548,8 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       }
       if (r.allele_ct > 2) {
         multi.push_back(q);
+      } else if (want_sums && (r.vrtype & 0x60u) && (e->global_to_local[first_variant + q0 + q] >= 0)) {
+        dos.push_back(q);  // (the reference has no sums for a record with several ALT alleles either: pgenlib_read.cc:8036)
       }
     }
     if (with_base_rec) {
@@ -599,17 +609,19 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       // the decode overwrites these rows before their records have been checked: from here on they hold nothing -- whatever happens below
       // (a malformed record, a failed copy, launch or sync) -- until load_rows_impl has counted them again
       std::fill(e->loaded.begin() + l_first, e->loaded.begin() + l_first + cnt, static_cast<uint8_t>(0));
+      std::fill(e->dos_has.begin() + l_first, e->dos_has.begin() + l_first + cnt, static_cast<uint8_t>(0));
       if (e->d_stored_inv) {
         HIP_TRY(e, hipMemsetAsync(e->d_stored_inv + l_first, 0, cnt, e->stream));  // (... and they will be in the file's orientation)
       }
     }
     const uint64_t lstride = into_image ? e->code_row_bytes : stride;
-    void *p_recs = nullptr, *p_rows = nullptr, *p_end = nullptr, *p_multi = nullptr, *p_mf = nullptr, *p_mi = nullptr, *p_inv = nullptr;
+    void *p_recs = nullptr, *p_rows = nullptr, *p_end = nullptr, *p_multi = nullptr, *p_mf = nullptr, *p_mi = nullptr, *p_inv = nullptr, *p_dos = nullptr, *p_sums = nullptr;
     if ((rc = dec_reserve(e, 1, rows * sizeof(ldp::PgenRecDesc), &p_recs)) ||
         (into_image ? 0 : (rc = dec_reserve(e, 2, static_cast<size_t>(rows) * stride, &p_rows))) ||
         (rc = dec_reserve(e, 3, rows * sizeof(uint64_t), &p_end)) || (rc = dec_reserve(e, 4, (multi.size() + 1) * sizeof(uint32_t), &p_multi)) ||
         (rc = dec_reserve(e, 5, (multi.size() + 1) * sizeof(double), &p_mf)) || (rc = dec_reserve(e, 6, (multi.size() + 1) * sizeof(uint32_t) + sizeof(int), &p_mi)) ||
-        (rc = dec_reserve(e, 7, rows + 8, &p_inv))) {
+        (rc = dec_reserve(e, 7, rows + 8, &p_inv)) || (rc = dec_reserve(e, 8, (dos.size() + 1) * sizeof(uint32_t), &p_dos)) ||
+        (rc = dec_reserve(e, 9, (dos.size() + 1) * 2 * sizeof(uint64_t), &p_sums))) {
       return rc;
     }
     int* d_err = reinterpret_cast<int*>(static_cast<uint32_t*>(p_mi) + multi.size() + 1);
@@ -618,6 +630,10 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     if (!multi.empty()) {
       memcpy(h_multi, multi.data(), multi.size() * sizeof(uint32_t));
       HIP_TRY(e, hipMemcpyAsync(p_multi, h_multi, multi.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    if (!dos.empty()) {
+      memcpy(h_dos, dos.data(), dos.size() * sizeof(uint32_t));
+      HIP_TRY(e, hipMemcpyAsync(p_dos, h_dos, dos.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     }
     HIP_TRY(e, hipMemsetAsync(d_err, 0, sizeof(int), e->stream));
     HIP_TRY(e, hipMemsetAsync(p_inv, 0, rows, e->stream));
@@ -640,7 +656,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     DA.maj_freq = static_cast<double*>(p_mf);
     DA.maj_idx = static_cast<uint32_t*>(p_mi);
     DA.row_inverse = static_cast<uint8_t*>(p_inv);
-    if (mapped && e->map_is_subset && (!e->d_map_mask) && !multi.empty()) {
+    if (mapped && e->map_is_subset && (!e->d_map_mask) && ((!multi.empty()) || !dos.empty())) {
       // (the device copy went with a re-plan or ldp_release_device(): the host's sample map is the master)
       std::vector<uint32_t> mask((static_cast<size_t>(e->map_raw_sample_ct) + 31) / 32 + 1, 0);
       for (uint32_t sm : e->sample_map) {
@@ -653,6 +669,9 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     DA.mask_ct = e->P.founder_ct;
     DA.phase_off = phase_off;
     DA.unphased = d_unphased;
+    DA.dosage_rec = static_cast<const uint32_t*>(p_dos);
+    DA.n_dosage = static_cast<uint32_t>(dos.size());
+    DA.dosage_sums = static_cast<uint64_t*>(p_sums);
     hipError_t krc = launch_pgen_main(DA, e->stream);
     if (krc != hipSuccess) {
       return hipfail(e, krc, "pgen_main_kernel launch");
@@ -664,6 +683,12 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       if (krc != hipSuccess) {
         return hipfail(e, krc, "pgen_phase_kernel launch");
       }
+    }
+    // the dosage sums, while every row is still the file's main track over all of the file's samples (the collapse below rewrites rows with
+    // several ALT alleles, the load behind it gathers the sample map's columns and may store a row inverted)
+    krc = launch_pgen_dosage(DA, e->stream);
+    if (krc != hipSuccess) {
+      return hipfail(e, krc, "pgen_dosage_kernel launch");
     }
     // the row the next launch's LD-compressed records may build on (taken BEFORE the multiallelic collapse rewrites rows:
     // an LD base is the main track as stored)
@@ -688,6 +713,9 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     if (!multi.empty()) {
       HIP_TRY(e, hipMemcpyAsync(h_maj_freq, p_mf, multi.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
       HIP_TRY(e, hipMemcpyAsync(h_maj_idx, p_mi, multi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    }
+    if (!dos.empty()) {
+      HIP_TRY(e, hipMemcpyAsync(h_sums, p_sums, dos.size() * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     }
     const double t_q = now_ms();
     HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -734,6 +762,12 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
           e->maj_freq[l] = h_maj_freq[k];
           e->mf_set[l] = 1;
         }
+      }
+      for (size_t k = 0; k < dos.size(); ++k) {
+        const int64_t l = e->global_to_local[first_variant + q0 + dos[k]];  // (owned: the list holds no others)
+        e->dos_ref[l] = h_sums[2 * k];
+        e->dos_alt[l] = h_sums[2 * k + 1];
+        e->dos_has[l] = 1;
       }
     }
   }

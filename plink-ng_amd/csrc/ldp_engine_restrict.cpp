@@ -97,8 +97,13 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
   // the host's per-row state at the new indices
   std::vector<double> new_mf(new_local);
   std::vector<uint8_t> new_mf_set(new_local), new_inv(new_local);
+  std::vector<uint64_t> new_dos_ref(new_local), new_dos_alt(new_local);
+  std::vector<uint8_t> new_dos_has(new_local);
   bool any_inv = false;
   for (uint32_t k = 0; k < new_local; ++k) {
+    new_dos_ref[k] = e->dos_ref[src[k]];
+    new_dos_alt[k] = e->dos_alt[src[k]];
+    new_dos_has[k] = e->dos_has[src[k]];
     new_mf[k] = e->maj_freq[src[k]];
     new_mf_set[k] = e->mf_set[src[k]];
     new_inv[k] = e->row_inv_loaded[src[k]];
@@ -145,7 +150,7 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
   }
   if (bounce_rows) {
     const size_t need = static_cast<size_t>(bounce_rows) * pitch;
-    for (int k = 0; k < 8; ++k) {  // (the decode scratch of ldp_load_pgen_records(), when it is there and large enough: its contents are per launch)
+    for (int k = 0; k < ldp_engine::kDecSlots; ++k) {  // (the decode scratch of ldp_load_pgen_records(), when it is there and large enough: its contents are per launch)
       if (e->dec.ptr[k] && (e->dec.cap[k] >= need)) {
         bounce = static_cast<uint8_t*>(e->dec.ptr[k]);
         break;
@@ -275,6 +280,10 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
       e->mf_set[k] = new_mf_set[k] ? 2 : 0;
     }
   }
+  // the dosage sums are sums over a row's samples: they travel with it
+  e->dos_ref.swap(new_dos_ref);
+  e->dos_alt.swap(new_dos_alt);
+  e->dos_has.swap(new_dos_has);
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // (the temporaries above are read until here)
   return LDP_OK;
 }

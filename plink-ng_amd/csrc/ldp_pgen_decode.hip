@@ -58,13 +58,15 @@ struct ByteCursor {
     ok = false;
     return 0;
   }
+  // (the cursor advances whether or not the bytes are there -- nothing is read through a cursor that is not ok, and u8() checks p itself --:
+  // written as `if (too few) fail; p += n`, hipcc 6.x turned the pointer into a scalar select on the comparison, sank the select below the
+  // branch on the same comparison and dropped the instruction that had put the comparison into SCC, in pgen_dosage_kernel alone; the select
+  // then read the SCC of id_width()'s last comparison, and the id lists of files with more than 256 samples were parsed two bytes early)
   __device__ __forceinline__ bool skip(uint64_t n) {
-    if (static_cast<uint64_t>(end - p) < n) {
-      ok = false;
-      return false;
-    }
+    const bool fits = ok && (static_cast<uint64_t>(end - p) >= n);
     p += n;
-    return true;
+    ok = fits;
+    return fits;
   }
 };
 
@@ -1128,7 +1130,239 @@ __global__ __launch_bounds__(kThreads) void pgen_phase_kernel(PgenDecodeArgs A) 
   }
 }
 
+// ---- dosage tracks: the two allele dosage sums (--indep-pairwise on imputed files) ------------------------------------------
+// pgen_spec.tex:566-606; GetBasicGenotypeCountsAndDosage16s, pgenlib_read.cc:7917-8190; the host's restatement is
+// ldp_pgen_dosage_sums (ldp_pgen.cpp), and this kernel computes the same two integers from the same bytes.  Behind the main track
+// of a record with one ALT allele: [the hardcall-phase track, when the type byte has bit 4: 1 + het_ct bits, and -- bit 0 of its
+// first byte set -- one phaseinfo bit per phasepresent bit,] then the dosages of the samples that have one, 16 bits each
+// (16384 per ALT copy), located by kind (type byte bits 5-6): 0x20 a sample-id difflist, 0x40 every sample (65535 = none),
+// 0x60 one presence bit per sample.  A sample of the mask contributes its dosage where it has one, its hardcall otherwise,
+// nothing when it has neither.  One workgroup per listed record, on its decoded row while that is still the file's main track
+// over all of the file's samples; everything is integer arithmetic.
+__device__ __forceinline__ uint64_t spread32(uint32_t x) {
+  return static_cast<uint64_t>(spread16(x)) | (static_cast<uint64_t>(spread16(x >> 16)) << 32);
+}
+
+// the workgroup's sum of one number per thread, in every thread
+template <int NT>
+__device__ __forceinline__ uint64_t block_sum64(uint64_t mine, uint64_t* s_red, uint32_t tid) {
+#pragma unroll
+  for (uint32_t off = 32; off; off >>= 1) {
+    mine += __shfl_down(static_cast<unsigned long long>(mine), off, 64);
+  }
+  __syncthreads();  // (s_red may still be read from the previous use)
+  if ((tid & 63) == 0) {
+    s_red[tid >> 6] = mine;
+  }
+  __syncthreads();
+  uint64_t all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < NT / 64; ++w) {
+    all += s_red[w];
+  }
+  return all;
+}
+
+__global__ __launch_bounds__(kThreads) void pgen_dosage_kernel(PgenDecodeArgs A) {
+  __shared__ uint32_t s_tmp[kThreads];
+  __shared__ uint64_t s_red[kThreads / 64];
+  __shared__ int s_bad;
+  __shared__ const uint8_t* s_ptr;
+  const uint32_t m = blockIdx.x;
+  const uint32_t v = A.dosage_rec[m];
+  const uint32_t tid = threadIdx.x;
+  const PgenRecDesc R = A.recs[v];
+  const uint32_t n = A.sample_ct;
+  const uint32_t* row = reinterpret_cast<const uint32_t*>(A.rows + static_cast<uint64_t>(v) * A.stride);
+  const uint32_t* __restrict__ smask = A.sample_mask;
+  const uint32_t n_words = (n + 31) / 32;  // 32 samples = two code dwords (both inside the stride, zero behind the last sample)
+  const uint64_t m5 = 0x5555555555555555ull;
+  if (tid == 0) {
+    s_bad = 0;
+    s_ptr = nullptr;
+  }
+  auto valid32 = [&](uint32_t w) -> uint32_t { return (n - 32 * w >= 32) ? 0xffffffffu : ((1u << (n - 32 * w)) - 1u); };
+  auto mask32 = [&](uint32_t w) -> uint32_t { return (smask ? smask[w] : 0xffffffffu) & valid32(w); };
+  auto codes64 = [&](uint32_t w) -> uint64_t { return static_cast<uint64_t>(row[2 * w]) | (static_cast<uint64_t>(row[2 * w + 1]) << 32); };
+  auto in_mask = [&](uint32_t sample) -> bool { return (!smask) || ((smask[sample >> 5] >> (sample & 31)) & 1u); };
+  // ---- hardcall counts of the masked samples; het calls of all samples (they size the phase track)
+  uint64_t my_het_all = 0, my_g0 = 0, my_g1 = 0, my_g2 = 0;
+  for (uint32_t w = tid; w < n_words; w += kThreads) {
+    const uint64_t g = codes64(w);
+    const uint64_t lo = g & m5, hi = (g >> 1) & m5;
+    const uint64_t V = spread32(valid32(w)), M = spread32(mask32(w));
+    my_het_all += static_cast<uint64_t>(__popcll(lo & ~hi & V));
+    my_g0 += static_cast<uint64_t>(__popcll(~(lo | hi) & M));
+    my_g1 += static_cast<uint64_t>(__popcll(lo & ~hi & M));
+    my_g2 += static_cast<uint64_t>(__popcll(hi & ~lo & M));
+  }
+  // (every thread holds the same sums; readfirstlane says so to the compiler, and the byte cursor below -- advanced by amounts that depend on
+  // them -- stays in scalar registers, as in the other kernels of this file)
+  const uint64_t het_all = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(block_sum64<kThreads>(my_het_all, s_red, tid)));
+  const uint64_t g0 = block_sum64<kThreads>(my_g0, s_red, tid);
+  const uint64_t g1 = block_sum64<kThreads>(my_g1, s_red, tid);
+  const uint64_t g2 = block_sum64<kThreads>(my_g2, s_red, tid);
+  const uint8_t* rec_begin = A.bytes + R.off;
+  const uint8_t* rec_end = rec_begin + R.len;
+  ByteCursor c{A.bytes + A.main_end[v], rec_end, true};
+  bool bad = (c.p < rec_begin) || (c.p > rec_end) || (R.allele_ct != 2);
+  // ---- the hardcall-phase track in front (every thread the same cursor)
+  if ((R.vrtype & 0x10u) && !bad) {
+    const uint64_t first = 1 + het_all / 8;
+    if (static_cast<uint64_t>(c.end - c.p) < first) {
+      bad = true;
+    } else {
+      uint64_t skip = first;
+      if (c.p[0] & 1u) {
+        uint64_t mine = 0;
+        for (uint64_t b = tid; b < first; b += kThreads) {
+          mine += static_cast<uint64_t>(__popc(static_cast<uint32_t>(c.p[b])));
+        }
+        const uint64_t present = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(block_sum64<kThreads>(mine, s_red, tid)));
+        skip += (present - 1 + 7) / 8;
+      }
+      if (!c.skip(skip)) {
+        bad = true;
+      }
+    }
+  }
+  // ---- the dosages: their sum and number over the masked samples, and the hardcalls they replace
+  uint64_t alt = 0, dosage_ct = 0, r0 = 0, r1 = 0, r2 = 0;
+  const uint32_t kind = R.vrtype & 0x60u;
+  if (bad) {
+    // (nothing is read)
+  } else if (kind == 0x40u) {
+    const uint8_t* vals = c.p;
+    if (!c.skip(2ull * n)) {
+      bad = true;
+    } else {
+      for (uint32_t s = tid; s < n; s += kThreads) {
+        const uint32_t d = read_le(vals + 2ull * s, 2);
+        if ((d != 65535u) && in_mask(s)) {
+          alt += d;
+          ++dosage_ct;
+        }
+      }
+    }
+  } else if (kind == 0x60u) {
+    const uint8_t* bits = c.p;
+    const uint64_t nbits_bytes = (static_cast<uint64_t>(n) + 7) / 8;
+    if (!c.skip(nbits_bytes)) {
+      bad = true;
+    } else {
+      // a thread's samples are consecutive: the rank of its first value is the number of presence bits in front of them
+      const uint32_t per = (n_words + kThreads - 1) / kThreads;
+      const uint32_t w0 = min(tid * per, n_words), w1 = min(w0 + per, n_words);
+      auto present32 = [&](uint32_t w) -> uint32_t { return dword_of_bytes(bits, nbits_bytes, w) & valid32(w); };
+      uint32_t mine = 0;
+      for (uint32_t w = w0; w < w1; ++w) {
+        mine += __popc(present32(w));
+      }
+      uint32_t total = 0;
+      uint64_t k = block_exclusive<kThreads>(mine, s_tmp, tid, &total);
+      const uint8_t* vals = c.p;
+      if (!c.skip(2ull * total)) {
+        bad = true;
+      } else {
+        for (uint32_t w = w0; w < w1; ++w) {
+          const uint32_t pw = present32(w);
+          if (!pw) {
+            continue;
+          }
+          const uint32_t mw = mask32(w);
+          for (uint32_t x = pw; x; x &= x - 1, ++k) {
+            if ((mw >> __builtin_ctz(x)) & 1u) {
+              alt += read_le(vals + 2 * k, 2);
+              ++dosage_ct;
+            }
+          }
+          const uint64_t g = codes64(w);
+          const uint64_t lo = g & m5, hi = (g >> 1) & m5, PM = spread32(pw & mw);
+          r0 += static_cast<uint64_t>(__popcll(~(lo | hi) & PM));
+          r1 += static_cast<uint64_t>(__popcll(lo & ~hi & PM));
+          r2 += static_cast<uint64_t>(__popcll(hi & ~lo & PM));
+        }
+      }
+    }
+  } else if (kind == 0x20u) {
+    Difflist D;
+    if (!difflist_open<kThreads>(c, n, false, s_tmp, tid, &D)) {
+      bad = true;
+    } else if (D.L) {
+      // where the list ends -- and the values begin -- only the walk of its last group tells
+      const bool last = (D.g0 < D.g1) && (D.g1 == D.G);
+      if (last) {
+        Difflist tail = D;
+        for (uint32_t g = tail.g0; g + 1 < tail.g1; ++g) {
+          tail.mine += static_cast<uint32_t>(tail.sizes[g]) + 63u;
+        }
+        tail.g0 = tail.g1 - 1;
+        const uint8_t* list_end = nullptr;
+        if (difflist_walk(tail, rec_end, n, &list_end, [](uint32_t, uint32_t) {})) {
+          s_ptr = list_end;
+        }
+      }
+      __syncthreads();
+      const uint8_t* vals = s_ptr;
+      if ((!vals) || (static_cast<uint64_t>(rec_end - vals) < 2ull * D.L)) {
+        bad = true;
+      } else {
+        const uint8_t* unused = nullptr;
+        if (!difflist_walk(D, rec_end, n, &unused, [&](uint32_t id, uint32_t k) {
+              if (in_mask(id)) {
+                alt += read_le(vals + 2ull * k, 2);
+                ++dosage_ct;
+                const uint32_t code = (row[id >> 4] >> (2 * (id & 15))) & 3u;
+                r0 += (code == 0) ? 1u : 0u;
+                r1 += (code == 1) ? 1u : 0u;
+                r2 += (code == 2) ? 1u : 0u;
+              }
+            })) {
+          bad = true;
+        }
+      }
+    }
+  } else {
+    bad = true;  // (the launch lists records with a dosage track)
+  }
+  if (bad) {
+    s_bad = 1;
+  }
+  __syncthreads();
+  if (s_bad) {
+    if (tid == 0) {
+      atomicCAS(A.error, 0, static_cast<int>(v) + 1);
+    }
+    return;
+  }
+  alt = block_sum64<kThreads>(alt, s_red, tid);
+  dosage_ct = block_sum64<kThreads>(dosage_ct, s_red, tid);
+  if (kind == 0x40u) {
+    // (every called sample has a value: the hardcalls are all replaced)
+    r0 = g0;
+    r1 = g1;
+    r2 = g2;
+  } else {
+    r0 = block_sum64<kThreads>(r0, s_red, tid);
+    r1 = block_sum64<kThreads>(r1, s_red, tid);
+    r2 = block_sum64<kThreads>(r2, s_red, tid);
+  }
+  if (tid == 0) {
+    const uint64_t alt_all = alt + (2 * (g2 - r2) + (g1 - r1)) * 16384ull;
+    A.dosage_sums[2ull * m] = (dosage_ct + (g0 + g1 + g2) - (r0 + r1 + r2)) * 32768ull - alt_all;
+    A.dosage_sums[2ull * m + 1] = alt_all;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_pgen_dosage(const PgenDecodeArgs& a, hipStream_t stream) {
+  if (!a.n_dosage) {
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(pgen_dosage_kernel, dim3(a.n_dosage), dim3(kThreads), 0, stream, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_pgen_phase(const PgenDecodeArgs& a, uint32_t n_records, hipStream_t stream) {
   if (!n_records || !a.phase_off) {

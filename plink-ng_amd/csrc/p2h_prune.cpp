@@ -75,6 +75,7 @@ struct PruneJob {
   ldp_params P;
   bool duplicate_ids = false;
   double t_tables_done = 0, t_planned = 0, t_load0 = 0, t_load1 = 0, t_run1 = 0;
+  double t_rows0 = 0, t_rows1 = 0;  // load_diploid_rows(): the file -> HBM leg itself
   // the count filters decided from the engine's records (Session::device_filter)
   uint64_t filter_rows_compacted = 0, filter_rows_bounced = 0;
   double filter_ms_compact = 0.0, filter_s = 0.0, filter_ms_recount = 0.0;
@@ -686,6 +687,7 @@ struct PruneJob {
   // GetMajIdx's rule (REF unless its frequency is below 0.5).  The rows themselves stay the hardcalls.
   void set_dosage_frequencies() {
     if (S.has_dosage) {
+      const double t_dos0 = now_s();
       std::vector<uint32_t> todo;
       for (uint32_t qq = 0; qq < m_ct; ++qq) {
         const uint32_t raw_v = inc[mk[qq]];
@@ -699,12 +701,47 @@ struct PruneJob {
         todo.push_back(qq);
       }
       std::vector<double> mfs(todo.size(), 0.0);
+      size_t from_device = 0, from_host = 0;
       {
         std::vector<uint32_t> raw_todo(todo.size());
         for (size_t q = 0; q < todo.size(); ++q) {
           raw_todo[q] = inc[mk[todo[q]]];
         }
-        S.need_dosage_sums(raw_todo);
+        // The engine that loaded a variant's record summed its dosage track where the bytes landed (ldp_load_pgen_records ->
+        // ldp_get_dosage_sums; under --gpus N every run lies in the engine that owns it).  What is left -- --debug-host-decode,
+        // --indep-pairphase rows, rows the host built -- takes the host pass over the file.
+        std::vector<uint32_t> host_todo;
+        if (!todo.empty()) {
+          const uint32_t q_lo = todo.front(), q_n = todo.back() - todo.front() + 1;
+          std::vector<uint64_t> ref_dd(q_n), alt_dd(q_n);
+          std::vector<uint8_t> has(q_n), any(q_n, 0);
+          std::vector<std::pair<uint64_t, uint64_t>> got(q_n);
+          for (int r = 0; (r < world) && !g_dbg.host_decode; ++r) {
+            if (ldp_get_dosage_sums(eng[r], q_lo, q_n, ref_dd.data(), alt_dd.data(), has.data())) {
+              die(16, "\nError: %s\n", ldp_last_error(eng[r]));
+            }
+            for (uint32_t k = 0; k < q_n; ++k) {
+              if (has[k] && !any[k]) {
+                any[k] = 1;
+                got[k] = {ref_dd[k], alt_dd[k]};
+              }
+            }
+          }
+          for (size_t q = 0; q < todo.size(); ++q) {
+            if (S.dosage_sums.count(raw_todo[q])) {
+              continue;  // (the host's filter pass before the load has them)
+            }
+            const uint32_t k = todo[q] - q_lo;
+            if (any[k]) {
+              S.dosage_sums[raw_todo[q]] = got[k];
+              ++from_device;
+            } else {
+              host_todo.push_back(raw_todo[q]);
+            }
+          }
+        }
+        from_host = host_todo.size();
+        S.need_dosage_sums(host_todo);
         for (size_t q = 0; q < todo.size(); ++q) {
           const std::pair<uint64_t, uint64_t>& dd = S.dosage_sums[raw_todo[q]];
           const uint64_t tot = dd.first + dd.second;
@@ -712,15 +749,24 @@ struct PruneJob {
           mfs[q] = (ref_freq < 0.5) ? (1.0 - ref_freq) : ref_freq;
         }
       }
-      for (size_t q = 0; q < todo.size(); ++q) {
+      // one call per run of consecutive variants per engine
+      for (size_t q = 0; q < todo.size();) {
+        size_t run = 1;
+        while ((q + run < todo.size()) && (todo[q + run] == todo[q] + run)) {
+          ++run;
+        }
         for (int r = 0; r < world; ++r) {
-          if (ldp_set_maj_freqs(eng[r], todo[q], 1, &mfs[q])) {
+          if (ldp_set_maj_freqs(eng[r], todo[q], static_cast<uint32_t>(run), &mfs[q])) {
             die(16, "\nError: %s\n", ldp_last_error(eng[r]));
           }
         }
+        q += run;
       }
       if (A.timing) {
-        logprintf("\n[timing] allele frequencies of %zu variants from their dosages\n", todo.size());
+        // (what lies between the end of the load and the first pair launch: this pass, and the rows the host builds before it)
+        logprintf("\n[timing] allele frequencies of %zu variants from their dosages: %zu summed on the device by the load, %zu by the host pass over the file, %.3f s "
+                  "(rows loaded in %.3f s; %.3f s from the end of the load to the end of this pass)\n",
+                  todo.size(), from_device, from_host, now_s() - t_dos0, t_rows1 - t_rows0, now_s() - t_rows1);
       }
     }
   }
@@ -1199,7 +1245,9 @@ struct PruneJob {
       // load first, then filter and plan; the ID check and --indep-preferred are about the variants the filters leave
       t_load0 = now_s();
       set_row_geometry();
+      t_rows0 = now_s();
       load_diploid_rows();
+      t_rows1 = now_s();
       if (S.mind_device && mind_on_device()) {
         return 0;  // (S.restart: main() starts over without the removed samples)
       }
@@ -1228,7 +1276,9 @@ struct PruneJob {
       t_run1 = 0;
       if (subcontig_ct) {
         if (!S.device_filter) {
+          t_rows0 = now_s();
           load_diploid_rows();
+          t_rows1 = now_s();
         }
         patch_host_built_rows();
         set_dosage_frequencies();
