@@ -900,3 +900,70 @@ def compare_decisions(got, want, lo, stats, r2, counters=None, limit=10):
                 "four_tile_launches", "wide_tiles", "mfma_skipped_product_stages", "sparse_exact_pairs", "pred_true")
         lines.append("  counters: " + ", ".join("%s=%s" % (k, counters[k]) for k in keys if k in counters))
     return len(bad), "\n".join(lines)
+
+
+# ---------------------------------------------------------------- the engine's columns for rows that are re-laid out on the way in
+def hap_raw_codes(raw, phaseinfo):
+    """LDP_GENO_PHASED rows as the engine's image holds them: (M, S) REF-based codes + (M, S) phaseinfo bits -> (M, 2S) codes of
+    the haplotype "samples", 2 = the haplotype carries ALT, 0 = it does not, 3 on both = a missing call.  Sample s owns columns
+    2s and 2s + 1, and a het call's ALT allele goes to column 2s + 1 when its phaseinfo bit is set ("1|0", oracle_hapsplit),
+    to column 2s otherwise: the bit order of HapsplitMustPhased's output (pgenlib_misc.cc:1917: het + phaseinfo -> binary 10),
+    which the count pass keeps (hap_codes_of_16 in ldp_codes.hip) and tests/test_input_forms_reference.py compares with the
+    oracle's rows bit by bit.
+    The prune decision cov^2 > thr var1 var2 does not depend on which allele a row is oriented on (a flipped row changes the
+    sign of its sum and of the dot product, hence of cov, and nothing else), so band_pair_stats / band_decisions over these
+    codes -- or over mapped_raw_codes, or over REF-coded rows of any other input form -- is the one reference for every form
+    in which rows reach the image; the statistics themselves are 4 x the reference's haplotype ones
+    (test_pairphase.py::test_haplotype_statistics_are_a_quarter_of_the_genotype_coded_ones), the decisions the same bits."""
+    raw = np.asarray(raw)
+    info = np.asarray(phaseinfo).astype(bool)
+    m, s = raw.shape
+    het = raw == 1
+    out = np.empty((m, 2 * s), dtype=np.uint8)
+    out[:, 0::2] = np.where(raw == 3, 3, np.where((raw == 2) | (het & ~info), 2, 0))
+    out[:, 1::2] = np.where(raw == 3, 3, np.where((raw == 2) | (het & info), 2, 0))
+    return out
+
+
+def mapped_raw_codes(raw, src, het_to_missing):
+    """LDP_GENO_MAPPED rows as the engine's image holds them: column f = sample src[f] of the file's REF-based row, a het call
+    turned into a missing one where het_to_missing[f] is set (ldp_set_sample_map).  The statistics of every pair are those of
+    these columns (band_pair_stats); only the major allele -- which no decision depends on, see hap_raw_codes -- is counted
+    before the substitution (host_rows)."""
+    cols = np.asarray(raw)[:, np.asarray(src, dtype=np.int64)].copy()
+    cols[(cols == 1) & (np.asarray(het_to_missing)[None, :] != 0)] = 3
+    return cols
+
+
+def host_rows(raw, src, het_missing):
+    """numpy restatement of the host builder of sample-mapped rows: (inverse-coded rows, maj_freq, ALT-is-major flags)"""
+    cols = raw[:, src]                                   # raw REF codes of the engine's columns
+    ref_ct = 2 * (cols == 0).sum(1) + (cols == 1).sum(1)
+    alt_ct = 2 * (cols == 2).sum(1) + (cols == 1).sum(1)
+    tot = ref_ct + alt_ct
+    ref_freq = np.full(raw.shape[0], 0.5)
+    nz = tot > 0
+    ref_freq[nz] = ref_ct[nz].astype(np.float64) * (1.0 / tot[nz].astype(np.float64))
+    alt_major = ~(ref_freq >= 0.5)
+    mf = np.where(alt_major, np.maximum(1.0 - ref_freq, 0.0), ref_freq)
+    out = cols.copy()
+    out[(cols == 1) & (het_missing[None, :] != 0)] = 3
+    inv = np.array([2, 1, 0, 3], dtype=out.dtype)
+    out[alt_major] = inv[out[alt_major]]
+    return out, mf, alt_major
+
+
+def major_oriented_planes(codes, alt_major=None):
+    """what LdPruneEngine.planes() returns for a row whose image holds `codes` ((N,) REF-based codes): the hom and ref2het bit
+    planes of the row oriented on its major allele (uint32 words, sample s -> bit s % 32 of word s // 32; padding clear).
+    alt_major: the major allele where the codes alone do not decide it (sample-mapped rows: host_rows)"""
+    codes = np.asarray(codes)
+    if alt_major is None:
+        ref_ct = 2 * int((codes == 0).sum()) + int((codes == 1).sum())
+        tot = ref_ct + 2 * int((codes == 2).sum()) + int((codes == 1).sum())
+        alt_major = not ((ref_ct * (1.0 / tot) if tot else 0.5) >= 0.5)
+    major = 2 if alt_major else 0
+    hom = pack_bits(((codes == 0) | (codes == 2))[None, :].astype(np.uint8)).view(np.uint32)[0]
+    r2h = pack_bits(((codes == major) | (codes == 1))[None, :].astype(np.uint8)).view(np.uint32)[0]
+    w = (len(codes) + 31) // 32
+    return hom[:w], r2h[:w]

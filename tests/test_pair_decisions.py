@@ -26,40 +26,41 @@ TOTALS = {"compared": 0, "candidate_pairs": 0, "engines": 0}
 
 
 class Reference:
-    """the rows of one case and what every engine over them must give: computed once per case, not per option set"""
+    """the rows of one case and what every engine over them must give: computed once per case, not per option set.
+    raw_for_stats: the image's columns as REF-based codes where they are not the rows that are loaded (haplotype columns of phased rows,
+    gathered columns of sample-mapped rows, the REF-coded form of INVERSE rows): the statistics, the founder count and -- unless `removed`
+    is given -- the prune set come from them.  removed: the prune set, where another oracle computes it (--indep-pairphase, host-built rows)."""
 
-    def __init__(self, pkg, raw, chr_idx, bps, window, step, is_bp, r2, order):
+    def __init__(self, pkg, raw, chr_idx, bps, window, step, is_bp, r2, order, raw_for_stats=None, removed=None):
         self.raw, self.chr_idx, self.bps = raw, np.asarray(chr_idx, dtype=np.uint32), bps
         self.window, self.step, self.is_bp, self.r2, self.order = window, step, is_bp, r2, order
-        self.m, self.n = raw.shape
+        self.raw_for_stats = raw if raw_for_stats is None else raw_for_stats
+        self.m, self.n = self.raw_for_stats.shape
+        assert raw.shape[0] == self.m
         self.packed = T.pack_2bit(raw)
         eng = pkg.LdPruneEngine(self.n, window, step, is_bp, r2, order=order, device=0)
         eng.set_variants(self.chr_idx, bps)
         self.lo, self.cand = eng.band()
         eng.close()
-        self.stats = T.band_pair_stats(raw, self.lo)
+        self.stats = T.band_pair_stats(self.raw_for_stats, self.lo)
         assert len(self.stats) == self.cand
         self.dec = T.band_decisions(self.stats, r2)
-        inv, mf, _ = T.oracle_prepare(raw)
-        self.removed, _ = T.oracle_indep_pairwise(inv, self.n, self.chr_idx, bps if bps is not None else np.arange(self.m, dtype=np.uint32), mf, window,
-                                                  step, is_bp, r2, order)
+        if removed is None:
+            inv, mf, _ = T.oracle_prepare(self.raw_for_stats)
+            removed, _ = T.oracle_indep_pairwise(inv, self.n, self.chr_idx, bps if bps is not None else np.arange(self.m, dtype=np.uint32), mf, window,
+                                                 step, is_bp, r2, order)
+        self.removed = removed
 
 
-def decide(pkg, ref, options, expect=None, loads=None, label=""):
-    """one production run over ref's rows with `options`; (a)-(e); returns the counters"""
-    eng = pkg.LdPruneEngine(ref.n, ref.window, ref.step, ref.is_bp, ref.r2, order=ref.order, device=0)
-    for name, value in options.items():
-        eng.set_option(name, value)
-    eng.set_variants(ref.chr_idx, ref.bps)
-    for a, b in (loads or [(0, ref.m)]):
-        eng.load_genotypes_host(a, ref.packed[a:b], pkg.LDP_GENO_REF)
+def run_and_compare(pkg, eng, ref, options, expect=None, label="", totals=None):
+    """one production run of a loaded engine; (a)-(e); returns the counters"""
+    totals = TOTALS if totals is None else totals
     removed = eng.run()
     pred, outside = eng.last_pred(with_outside=True)
     c = eng.counters()
-    eng.close()
-    TOTALS["compared"] += len(pred)
-    TOTALS["candidate_pairs"] += c["candidate_pairs"]
-    TOTALS["engines"] += 1
+    totals["compared"] += len(pred)
+    totals["candidate_pairs"] += c["candidate_pairs"]
+    totals["engines"] += 1
     print("pairs compared: %d  (%s %s; %d true; launches %d, routes complete/sparse/general %d/%d/%d, sparse/four tile launches %d/%d, skipped product stages %d)"
           % (len(pred), label, options, int(pred.sum()), c["pair_kernel_launches"], c["route_complete_launches"], c["route_sparse_launches"],
              c["route_general_launches"], c["sparse_tile_launches"], c["four_tile_launches"], c["mfma_skipped_product_stages"]))
@@ -71,6 +72,29 @@ def decide(pkg, ref, options, expect=None, loads=None, label=""):
     assert np.array_equal(removed, ref.removed), (label, options, int(removed.sum()), int(ref.removed.sum()))   # (d)
     if expect is not None:
         expect(c)                                                                            # (e)
+    return c
+
+
+def decide(pkg, ref, options, expect=None, loads=None, label="", load=None, inspect=None, totals=None):
+    """one production run over ref's rows with `options`; (a)-(e); returns the counters.
+    load: a callable (pkg, eng, ref) that brings the rows into the planned engine instead of ldp_load_genotypes() from host memory (it may
+    plan the engine again, set a sample map or frequencies -- whatever its input form takes).  inspect: a callable (eng, counters) run
+    after the comparison, before the engine is closed."""
+    eng = pkg.LdPruneEngine(ref.n, ref.window, ref.step, ref.is_bp, ref.r2, order=ref.order, device=0)
+    try:
+        for name, value in options.items():
+            eng.set_option(name, value)
+        eng.set_variants(ref.chr_idx, ref.bps)
+        if load is not None:
+            load(pkg, eng, ref)
+        else:
+            for a, b in (loads or [(0, ref.m)]):
+                eng.load_genotypes_host(a, ref.packed[a:b], pkg.LDP_GENO_REF)
+        c = run_and_compare(pkg, eng, ref, options, expect, label, totals)
+        if inspect is not None:
+            inspect(eng, c)
+    finally:
+        eng.close()
     return c
 
 

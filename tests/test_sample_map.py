@@ -10,24 +10,6 @@ from test_host_logic import make_positions
 pytestmark = pytest.mark.gpu
 
 
-def host_rows(raw, src, het_missing):
-    """numpy restatement of the host builder: (inverse-coded rows, maj_freq)"""
-    cols = raw[:, src]                                   # raw REF codes of the engine's columns
-    ref_ct = 2 * (cols == 0).sum(1) + (cols == 1).sum(1)
-    alt_ct = 2 * (cols == 2).sum(1) + (cols == 1).sum(1)
-    tot = ref_ct + alt_ct
-    ref_freq = np.full(raw.shape[0], 0.5)
-    nz = tot > 0
-    ref_freq[nz] = ref_ct[nz].astype(np.float64) * (1.0 / tot[nz].astype(np.float64))
-    alt_major = ~(ref_freq >= 0.5)
-    mf = np.where(alt_major, np.maximum(1.0 - ref_freq, 0.0), ref_freq)
-    out = cols.copy()
-    out[(cols == 1) & (het_missing[None, :] != 0)] = 3
-    inv = np.array([2, 1, 0, 3], dtype=out.dtype)
-    out[alt_major] = inv[out[alt_major]]
-    return out, mf, alt_major
-
-
 @pytest.mark.parametrize("n_raw,males,nonmales,enc", [(90, 31, 29, "ref"), (257, 100, 64, "bed"), (1500, 700, 650, "ref"), (64, 64, 0, "ref"),
                                                        (333, 0, 300, "bed"), (70000, 33000, 36000, "ref")])
 def test_mapped_rows_match_host_built_rows(gpu_pkg, n_raw, males, nonmales, enc):
@@ -44,7 +26,7 @@ def test_mapped_rows_match_host_built_rows(gpu_pkg, n_raw, males, nonmales, enc)
     het = np.concatenate([np.ones(males, np.uint8), np.zeros(2 * nonmales, np.uint8)])
     fct = len(src)
     chr_idx, bps = make_positions(m, 2, 7)
-    rows, mf, alt_major = host_rows(raw, src, het)
+    rows, mf, alt_major = T.host_rows(raw, src, het)
 
     a = pkg.LdPruneEngine(fct, 40, 1, False, 0.3, device=0)
     a.set_variants(chr_idx, None)
@@ -102,7 +84,7 @@ def test_mapped_subset_with_long_runs(gpu_pkg, n_raw, keep, flag, enc):
     src = np.flatnonzero(rng.random(n_raw) < keep).astype(np.uint32)
     het = np.full(len(src), flag, np.uint8)
     chr_idx, bps = make_positions(m, 2, 9)
-    rows, mf, alt_major = host_rows(raw, src, het)
+    rows, mf, alt_major = T.host_rows(raw, src, het)
     a = pkg.LdPruneEngine(len(src), 30, 1, False, 0.3, device=0)
     a.set_variants(chr_idx, None)
     a.load_genotypes_host(0, T.pack_2bit(rows), pkg.LDP_GENO_INVERSE)
