@@ -118,6 +118,18 @@ int ldp_debug_get_sample_missing_stats(const ldp_engine* e, double* ms_kernel, u
  * chunks and over both engines when there are phase rows.  Any pointer may be NULL. */
 int ldp_debug_get_phased_filter(const ldp_engine* e, uint64_t* pairs_seen, uint64_t* pairs_dropped, double* ms_hethet, double* ms_tuples);
 
+/* The checkpoint statistics the count pass of the loads wrote for variants [first_variant, first_variant + n), as they lie on the device
+ * (csrc/ldp_device.h): cp_out receives n records of 144 bytes -- nine 16-byte slots: five remainder slots and the whole-row slot
+ * {double a, b}, then on a code-image engine the whole-row and two remainder slots {uint32 calls, sum z, sum z^2, flag} (left as
+ * allocated on a bit-plane engine) --, cp_gen_out n rows of 80 bytes -- five {uint32 calls, sum z, sum z^2, pad}, written on bit-plane
+ * engines only --, checkpoint_chunk the engine's five checkpoint chunks (0xffffffff = unused) and *n_checkpoints how many are in use.
+ * Any output pointer may be NULL.  Waits for the engine's stream, then copies: no kernel is launched.  LDP_ERR_STATE before a plan is
+ * on the device or for rows that are not loaded, LDP_ERR_UNSUPPORTED on a sharded engine. */
+int ldp_debug_get_cp_stats(ldp_engine* e, uint32_t first_variant, uint32_t n, void* cp_out, void* cp_gen_out, uint32_t* checkpoint_chunk, uint32_t* n_checkpoints);
+/* Which count kernel the last load's launch ran -- *is_codes 1 = codes_kernel (code image), 0 = prepare_kernel (bit-planes) -- and
+ * the <THREADS, ITERS> instantiation the row length picked (ITERS 0 = the rolled loop).  LDP_ERR_STATE before the first load. */
+int ldp_debug_get_count_pass(const ldp_engine* e, uint32_t* is_codes, uint32_t* threads, uint32_t* iters);
+
 /* ---- synthetic workload (benchmark / test support, not part of the reference seam) ---- */
 /* Deterministic genotype generator for the SURVEY.md 8(d) workload: rows [first_variant, +n_variants) of
  * REF-based codes (LDP_GENO_REF) written to `out` (host or device memory), each genotype a pure function of

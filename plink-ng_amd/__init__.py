@@ -96,6 +96,10 @@ class ldp_tile_routes(ctypes.Structure):
 PAIR_STATS_DTYPE = np.dtype([("nm", "<u4"), ("sum1", "<i4"), ("ssq1", "<u4"), ("sum2", "<i4"), ("ssq2", "<u4"), ("dot", "<i4")])
 R2_HIT_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4"), ("r2", "<f8")])
 PHASED_STATS_DTYPE = np.dtype([("valid_obs", "<u4"), ("sum0", "<u4"), ("sum1", "<u4"), ("known_dotprod", "<u4"), ("unknown_hethet", "<u4")])
+# the count pass's checkpoint statistics (csrc/ldp_device.h: cp_slot, cp_gen_slot; LdPruneEngine.cp_stats)
+CP_SLOT_DTYPE = np.dtype([("a", "<f8"), ("b", "<f8")])
+CP_GEN_SLOT_DTYPE = np.dtype([("nm_r", "<u4"), ("zs_r", "<u4"), ("zq_r", "<u4"), ("pad", "<u4")])
+CP_CHECKPOINTS, CP_GEN_FIRST, CP_GEN_CHECKPOINTS = 5, 2, 2
 VARIANT_REC_DTYPE = np.dtype([("nm_ct", "<u4"), ("sum", "<i4"), ("ssq", "<u4"), ("flags", "<u4"), ("n_homref", "<u4"),
                               ("n_het", "<u4"), ("n_homalt", "<u4"), ("reserved", "<u4")])
 
@@ -113,7 +117,7 @@ CABI_SYMBOLS = [
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
-    "ldp_get_dosage_sums",
+    "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass",
 ]
 
 
@@ -231,6 +235,8 @@ def lib():
     L.ldp_debug_set_variant_recs.argtypes = [vp, vp]
     L.ldp_debug_replay_pairs.argtypes = [vp, ctypes.c_uint64, u32p, u32p, u64p]
     L.ldp_debug_get_pred.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64, u64p]
+    L.ldp_debug_get_cp_stats.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, u32p, u32p]
+    L.ldp_debug_get_count_pass.argtypes = [vp, u32p, u32p, u32p]
     L.ldp_map_rows.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp), u64p]
     L.ldp_release_device.argtypes = [vp]
     L.ldp_restrict_variants.argtypes = [vp, u64p, ctypes.c_uint32, u32p, u32p]
@@ -999,6 +1005,31 @@ class LdPruneEngine:
         out = np.zeros(max(n, 1), dtype=VARIANT_REC_DTYPE)
         self._ck(self._L.ldp_get_variant_recs(self._h, first, n, out.ctypes.data_as(ctypes.c_void_p)))
         return out[:n]
+
+    def cp_stats(self, first=0, n=None):
+        """The checkpoint statistics of variants [first, first + n) as the count pass left them on the device (ldp_debug_get_cp_stats): a dict
+        with 'chunks' (the five checkpoint chunks, 0xffffffff = unused), 'n_checkpoints', 'cp' ((n, 6) of a, b: five remainder slots + the
+        whole row), 'gen' ((n, 3) of nm_r, zs_r, zq_r, pad: the whole row + two remainders; written on code-image engines) and 'cp_gen'
+        ((n, 5) of the same fields; written on bit-plane engines)."""
+        n = self.variant_ct - first if n is None else n
+        stride = CP_CHECKPOINTS + 1 + 1 + CP_GEN_CHECKPOINTS
+        raw = np.zeros((max(n, 1), stride * 16), dtype=np.uint8)
+        cp_gen = np.zeros((max(n, 1), CP_CHECKPOINTS), dtype=CP_GEN_SLOT_DTYPE)
+        chunks = np.zeros(CP_CHECKPOINTS, dtype=np.uint32)
+        n_cp = ctypes.c_uint32()
+        self._ck(self._L.ldp_debug_get_cp_stats(self._h, first, n, raw.ctypes.data_as(ctypes.c_void_p), cp_gen.ctypes.data_as(ctypes.c_void_p),
+                                                _ptr(chunks, ctypes.c_uint32), ctypes.byref(n_cp)))
+        split = (CP_CHECKPOINTS + 1) * 16
+        cp = np.ascontiguousarray(raw[:n, :split]).view(CP_SLOT_DTYPE).reshape(n, CP_CHECKPOINTS + 1)
+        gen = np.ascontiguousarray(raw[:n, split:]).view(CP_GEN_SLOT_DTYPE).reshape(n, 1 + CP_GEN_CHECKPOINTS)
+        return {"chunks": chunks, "n_checkpoints": int(n_cp.value), "cp": cp, "gen": gen, "cp_gen": cp_gen[:n]}
+
+    def count_pass(self):
+        """(is_codes, THREADS, ITERS) of the count kernel the last load launched (ldp_debug_get_count_pass): codes_kernel on the code image or
+        prepare_kernel on bit-planes, and the instantiation the row length picked (ITERS 0 = the rolled loop)."""
+        c, t, i = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._ck(self._L.ldp_debug_get_count_pass(self._h, ctypes.byref(c), ctypes.byref(t), ctypes.byref(i)))
+        return bool(c.value), int(t.value), int(i.value)
 
     def maj_freqs(self, first=0, n=None):
         n = self.variant_ct - first if n is None else n

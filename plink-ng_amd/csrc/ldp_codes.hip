@@ -525,28 +525,45 @@ hipError_t launch_unflip_rows(uint8_t* codes, uint64_t code_row_bytes, uint8_t* 
   return hipGetLastError();
 }
 
-hipError_t launch_codes(const PrepareArgs& a, hipStream_t stream) {
+hipError_t launch_codes(const PrepareArgs& a, hipStream_t stream, uint32_t* shape) {
   if (!a.n_variants) {
     return hipSuccess;
   }
   const uint64_t units = a.code_row_bytes / 16;
+  uint32_t unused_shape[2];
+  if (!shape) {
+    shape = unused_shape;
+  }
   // the geometry prepare_kernel was tuned to (config 2: 128 x 7 best; N = 500,000: 512 x 16), a unit = 64 samples in both
-#define LDP_CODES(T, I) hipLaunchKernelGGL((codes_kernel<T, I>), dim3(a.n_variants), dim3(T), 0, stream, a)
-  if (const char* shape = LDP_ENV("LDP_DEBUG_CODES_SHAPE")) {  // tuning aid: "64x13", "128x7nt", "256x4", "256x4nt"
-    const std::string sh(shape);
+#define LDP_CODES(T, I)                                                                         \
+  do {                                                                                          \
+    shape[0] = T;                                                                               \
+    shape[1] = I;                                                                               \
+    hipLaunchKernelGGL((codes_kernel<T, I>), dim3(a.n_variants), dim3(T), 0, stream, a);       \
+  } while (0)
+  if (const char* env_shape = LDP_ENV("LDP_DEBUG_CODES_SHAPE")) {  // tuning aid: "64x13", "128x7nt", "256x4", "256x4nt"
+    const std::string sh(env_shape);
     if ((sh == "64x13") && (units <= 64 * 13)) {
+      shape[0] = 64;
+      shape[1] = 13;
       hipLaunchKernelGGL((codes_kernel<64, 13>), dim3(a.n_variants), dim3(64), 0, stream, a);
       return hipGetLastError();
     }
     if ((sh == "128x7nt") && (units <= 128 * 7)) {
+      shape[0] = 128;
+      shape[1] = 7;
       hipLaunchKernelGGL((codes_kernel<128, 7, true>), dim3(a.n_variants), dim3(128), 0, stream, a);
       return hipGetLastError();
     }
     if ((sh == "256x4") && (units <= 256 * 4)) {
+      shape[0] = 256;
+      shape[1] = 4;
       hipLaunchKernelGGL((codes_kernel<256, 4>), dim3(a.n_variants), dim3(256), 0, stream, a);
       return hipGetLastError();
     }
     if ((sh == "256x4nt") && (units <= 256 * 4)) {
+      shape[0] = 256;
+      shape[1] = 4;
       hipLaunchKernelGGL((codes_kernel<256, 4, true>), dim3(a.n_variants), dim3(256), 0, stream, a);
       return hipGetLastError();
     }

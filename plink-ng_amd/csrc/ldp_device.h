@@ -400,10 +400,11 @@ struct PrepareArgs {
   int orient;                    // launch_codes(): store ALT-major rows inverted (major-allele-oriented image)
 };
 
-hipError_t launch_prepare(const PrepareArgs& a, hipStream_t stream);
+// shape (optional, both launchers): receives the <THREADS, ITERS> of the instantiation the row length picked (ldp_debug_get_count_pass)
+hipError_t launch_prepare(const PrepareArgs& a, hipStream_t stream, uint32_t* shape = nullptr);
 // the same for the code image: rows of any accepted encoding -> REF- (or INVERSE-) coded 2-bit rows + the per-variant records and
 // checkpoint statistics (in the image's own orientation); no bit-planes
-hipError_t launch_codes(const PrepareArgs& a, hipStream_t stream);
+hipError_t launch_codes(const PrepareArgs& a, hipStream_t stream, uint32_t* shape = nullptr);
 // arbitrary pairs from the code image (the integers in major-allele orientation, like launch_pair_stats_ref)
 // image rows [0, n) with stored_inv[v] != 0 back to the input's orientation, flags cleared (ldp_map_rows: the caller is about to see / rewrite them)
 hipError_t launch_unflip_rows(uint8_t* codes, uint64_t code_row_bytes, uint8_t* stored_inv, uint32_t n, hipStream_t stream);

@@ -1336,6 +1336,28 @@ void ldp_destroy(ldp_engine* e) {
   }
   if (e->gpu_ok) {
     (void)hipSetDevice(e->device);
+    // A load returns with its count pass still queued (ldp_load_pgen_records on device-resident rows queues it behind its last
+    // synchronisation), and an engine may be destroyed right behind it: nothing of the engine's is freed under work of its own, as in
+    // ldp_release_device() -- not left to what hipFree() happens to wait for on streams that do not synchronise with the null stream.
+    for (int k = 0; k < kPairStreams; ++k) {
+      if (e->pair_stream[k]) {
+        (void)hipStreamSynchronize(e->pair_stream[k]);
+      }
+    }
+    for (int q = 0; q < 2; ++q) {
+      if (e->tile_side.s[q]) {
+        (void)hipStreamSynchronize(e->tile_side.s[q]);
+      }
+      if (e->h2d_stream[q]) {
+        (void)hipStreamSynchronize(e->h2d_stream[q]);
+      }
+    }
+    if (e->copy_stream) {
+      (void)hipStreamSynchronize(e->copy_stream);
+    }
+    if (e->stream) {
+      (void)hipStreamSynchronize(e->stream);
+    }
     free_device(e);
     if (e->own_stream) {
       (void)hipStreamDestroy(e->stream);
@@ -1878,6 +1900,72 @@ int ldp_get_variant_recs(ldp_engine* e, uint32_t first_variant, uint32_t n, ldp_
     } else {
       memset(&out[q], 0, sizeof(ldp_variant_rec));
     }
+  }
+  return LDP_OK;
+}
+
+int ldp_debug_get_cp_stats(ldp_engine* e, uint32_t first_variant, uint32_t n, void* cp_out, void* cp_gen_out, uint32_t* checkpoint_chunk, uint32_t* n_checkpoints) {
+  if (!e) {
+    return LDP_ERR_INVALID;
+  }
+  if (!e->planned || !e->plan_uploaded || !e->d_cp_stats || !e->d_cp_gen) {
+    return fail(e, LDP_ERR_STATE, "ldp_debug_get_cp_stats: no plan on the device (load rows first)");
+  }
+  if (e->world > 1) {
+    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_debug_get_cp_stats: sharded engines are not supported");
+  }
+  if (static_cast<uint64_t>(first_variant) + n > e->variant_ct) {
+    return fail(e, LDP_ERR_INVALID, "variant range out of bounds");
+  }
+  for (uint32_t q = 0; q < n; ++q) {
+    const int64_t l = e->global_to_local[first_variant + q];
+    if ((l < 0) || !e->loaded[l]) {
+      return fail(e, LDP_ERR_STATE, "ldp_debug_get_cp_stats: a variant of the range is not loaded");
+    }
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  constexpr size_t kCpBytes = kCpStride * sizeof(cp_slot), kGenBytes = kCheckpoints * sizeof(cp_gen_slot);
+  for (uint32_t q = 0; q < n;) {  // one copy per run of consecutive local rows
+    const int64_t l0 = e->global_to_local[first_variant + q];
+    uint32_t run = 1;
+    while ((q + run < n) && (e->global_to_local[first_variant + q + run] == l0 + run)) {
+      ++run;
+    }
+    if (cp_out) {
+      HIP_TRY(e, hipMemcpy(static_cast<uint8_t*>(cp_out) + q * kCpBytes, e->d_cp_stats + static_cast<uint64_t>(l0) * kCpStride, run * kCpBytes, hipMemcpyDeviceToHost));
+    }
+    if (cp_gen_out) {
+      HIP_TRY(e, hipMemcpy(static_cast<uint8_t*>(cp_gen_out) + q * kGenBytes, e->d_cp_gen + static_cast<uint64_t>(l0) * kCheckpoints, run * kGenBytes, hipMemcpyDeviceToHost));
+    }
+    q += run;
+  }
+  if (checkpoint_chunk) {
+    for (int k = 0; k < kCheckpoints; ++k) {
+      checkpoint_chunk[k] = e->checkpoint_chunk[k];
+    }
+  }
+  if (n_checkpoints) {
+    *n_checkpoints = e->n_checkpoints;
+  }
+  return LDP_OK;
+}
+
+int ldp_debug_get_count_pass(const ldp_engine* e, uint32_t* is_codes, uint32_t* threads, uint32_t* iters) {
+  if (!e) {
+    return LDP_ERR_INVALID;
+  }
+  if (!e->count_pass[1]) {
+    return LDP_ERR_STATE;  // no load has launched a count pass
+  }
+  if (is_codes) {
+    *is_codes = e->count_pass[0];
+  }
+  if (threads) {
+    *threads = e->count_pass[1];
+  }
+  if (iters) {
+    *iters = e->count_pass[2];
   }
   return LDP_OK;
 }

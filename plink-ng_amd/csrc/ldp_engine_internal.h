@@ -343,6 +343,8 @@ struct ldp_engine {
   uint32_t* d_route = nullptr;             // [g]: which matrix-pipe kernel owns launch group g (route_kernel, when the group is queued); [groups]: other launches
   uint32_t checkpoint_chunk[kCheckpoints];
   uint32_t n_checkpoints = 0;
+  // the count pass of the last load: {1 = codes_kernel / 0 = prepare_kernel, THREADS, ITERS} of its launch; THREADS 0 = none yet (ldp_debug_get_count_pass)
+  uint32_t count_pass[3] = {0, 0, 0};
   bool pred_valid = false;     // a run has completed since the last load: d_pred holds its decisions (ldp_debug_get_pred)
   uint32_t* h_pred = nullptr;  // pinned; allocated when a run needs the dense rows (inspection runs, engines without pred_csr, the overflow fallback)
   // the predicate rows as CSR (ldp_pred_csr.hip), written by the device straight into these pinned buffers; h_csr_flag[0] = overflow

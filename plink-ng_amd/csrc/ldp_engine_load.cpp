@@ -292,7 +292,8 @@ int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void
         HIP_TRY(e, hipEventRecord(e->prep_ev0, e->stream));
         e->prep_pending = true;
       }
-      hipError_t krc = e->codes_format ? launch_codes(PA, e->stream) : launch_prepare(PA, e->stream);
+      e->count_pass[0] = e->codes_format ? 1u : 0u;
+      hipError_t krc = e->codes_format ? launch_codes(PA, e->stream, e->count_pass + 1) : launch_prepare(PA, e->stream, e->count_pass + 1);
       if (krc != hipSuccess) {
         return hipfail(e, krc, e->codes_format ? "codes_kernel launch" : "prepare_kernel launch");
       }

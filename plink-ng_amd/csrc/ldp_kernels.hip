@@ -727,14 +727,23 @@ hipError_t launch_tile_route(const TileRouteArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_prepare(const PrepareArgs& a, hipStream_t stream) {
+hipError_t launch_prepare(const PrepareArgs& a, hipStream_t stream, uint32_t* shape) {
   if (!a.n_variants) {
     return hipSuccess;
+  }
+  uint32_t unused_shape[2];
+  if (!shape) {
+    shape = unused_shape;
   }
   const uint32_t pairs = (a.chunks * kChunkDwords + 1) / 2;  // pairs of plane dwords per row
   // Few threads with many 16-byte loads in flight each beat many threads with few (config 2: 128 x 7 runs at
   // 4.75 ms, 256 x 4 at 5.0, 512 x 2 at 7.1, one wave x 13 at 5.6): up to 8 register-resident iterations per thread.
-#define LDP_PREP(T, I) hipLaunchKernelGGL((prepare_kernel<T, I>), dim3(a.n_variants), dim3(T), 0, stream, a)
+#define LDP_PREP(T, I)                                                                          \
+  do {                                                                                          \
+    shape[0] = T;                                                                               \
+    shape[1] = I;                                                                               \
+    hipLaunchKernelGGL((prepare_kernel<T, I>), dim3(a.n_variants), dim3(T), 0, stream, a);     \
+  } while (0)
   if (pairs <= 128 * 2) {
     LDP_PREP(128, 2);
   } else if (pairs <= 128 * 4) {

@@ -967,3 +967,152 @@ def major_oriented_planes(codes, alt_major=None):
     r2h = pack_bits(((codes == major) | (codes == 1))[None, :].astype(np.uint8)).view(np.uint32)[0]
     w = (len(codes) + 31) // 32
     return hom[:w], r2h[:w]
+
+
+# ---------------------------------------------------------------- the count pass's checkpoint statistics, from the image row's codes
+CP_CHECKPOINTS, CP_GEN_FIRST, CP_GEN_CHECKPOINTS = 5, 2, 2   # csrc/ldp_device.h: kCheckpoints, kGenCheckpointFirst, kGenCheckpoints
+CP_CHUNK_SAMPLES = 512
+CP_STEPS = (0.012, 0.04, 0.08, 0.16, 0.36)
+CP_UNUSED = 0xffffffff
+
+
+def checkpoint_chunks(n, r2):
+    """The k-chunks (512 samples) at which a prune engine over n samples places its checkpoints, the rule of csrc/ldp_engine.cpp
+    restated: none below four chunks; otherwise the fractions 1 - sqrt(r2) + CP_STEPS that stay below 0.93, each times the chunk
+    count and rounded up, kept when strictly above the previous one and below the chunk count."""
+    chunks = (n + CP_CHUNK_SAMPLES - 1) // CP_CHUNK_SAMPLES
+    out = []
+    if chunks >= 4:
+        f0 = 1.0 - float(np.sqrt(np.float64(r2)))
+        for step in CP_STEPS:
+            f = f0 + step
+            if f < 0.93:
+                c = int(np.ceil(chunks * f))
+                if c and c < chunks and (not out or c > out[-1]):
+                    out.append(c)
+    return out
+
+
+def cp_tv_scale(r2):
+    return float(np.sqrt(np.sqrt(np.float64(r2) * (1 + K_SMALL_EPSILON)) * (1.0 - 1e-6)))
+
+
+def cp_reference(image_codes, n, chunks_list, r2):
+    """What the count pass stores per variant (csrc/ldp_device.h: cp_slot, cp_gen_slot), from the codes of the FINAL image rows:
+    image_codes (M, n), 0 / 1 / 2 / 3 as the image holds them (the raw codes with 0 <-> 2 swapped where the engine stores the row
+    inverted).  x = +1 / 0 / -1 and z = 0 / 1 / 2 for codes 0 / 1 / 2.  chunks_list: the checkpoints in use (checkpoint_chunks); the
+    others give zeros.  Returns a dict of int64 (M, 5) arrays over the samples >= 512 * chunk -- hom_r (codes 0 and 2), s_r (sum x),
+    calls_r, zs_r (sum z), zq_r (sum z^2) --, the whole-row int64 (M,) arrays hom, S, calls, zs, zq, and the float64 (M, 6) arrays a, b:
+        slot k < 5: a = s_r sqrt(n / n_r), b = sqrt(n (hom_r - s_r^2 / n_r)), n_r = n - 512 chunk
+        slot 5:     a = S,                 b = sqrt(n hom - S^2) cp_tv_scale(r2)
+    every operation a separate float64 rounding, in the order written."""
+    codes = np.asarray(image_codes)
+    m = codes.shape[0]
+    assert codes.shape[1] == n and len(chunks_list) <= CP_CHECKPOINTS
+    n_chunks = (n + CP_CHUNK_SAMPLES - 1) // CP_CHUNK_SAMPLES
+    per = np.zeros((3, m, n_chunks + 1), dtype=np.int64)    # per code and chunk; a zero behind the last chunk
+    for c in range(3):
+        hit = np.zeros((m, n_chunks * CP_CHUNK_SAMPLES), dtype=np.uint8)
+        hit[:, :n] = codes == c
+        per[c, :, :n_chunks] = hit.reshape(m, n_chunks, CP_CHUNK_SAMPLES).sum(2, dtype=np.int64)
+    suffix = np.cumsum(per[:, :, ::-1], axis=2)[:, :, ::-1]   # [c, v, k]: code-c calls in chunks >= k
+    out = {}
+    out["hom"] = suffix[0, :, 0] + suffix[2, :, 0]
+    out["S"] = suffix[0, :, 0] - suffix[2, :, 0]
+    out["calls"] = out["hom"] + suffix[1, :, 0]
+    out["zs"] = suffix[1, :, 0] + 2 * suffix[2, :, 0]
+    out["zq"] = suffix[1, :, 0] + 4 * suffix[2, :, 0]
+    for name in ("hom_r", "s_r", "calls_r", "zs_r", "zq_r"):
+        out[name] = np.zeros((m, CP_CHECKPOINTS), dtype=np.int64)
+    a = np.zeros((m, CP_CHECKPOINTS + 1), dtype=np.float64)
+    b = np.zeros((m, CP_CHECKPOINTS + 1), dtype=np.float64)
+    nn = np.float64(n)
+    for k, chunk in enumerate(chunks_list):
+        assert 0 < chunk < n_chunks
+        c0, c1, c2 = (suffix[c, :, chunk] for c in range(3))
+        out["hom_r"][:, k] = c0 + c2
+        out["s_r"][:, k] = c0 - c2
+        out["calls_r"][:, k] = c0 + c1 + c2
+        out["zs_r"][:, k] = c1 + 2 * c2
+        out["zq_r"][:, k] = c1 + 4 * c2
+        n_r = np.float64(n - CP_CHUNK_SAMPLES * chunk)
+        s_r = (c0 - c2).astype(np.float64)
+        v_r = np.maximum((c0 + c2).astype(np.float64) - (s_r * s_r) / n_r, 0.0)
+        a[:, k] = s_r * np.sqrt(nn / n_r)
+        b[:, k] = np.sqrt(nn * v_r)
+    S = out["S"].astype(np.float64)
+    a[:, CP_CHECKPOINTS] = S
+    b[:, CP_CHECKPOINTS] = np.sqrt(np.maximum(nn * out["hom"].astype(np.float64) - S * S, 0.0)) * cp_tv_scale(r2)
+    out["a"], out["b"] = a, b
+    return out
+
+
+def cp_recover(a, b, n, chunks_list):
+    """the integers back from the remainder slots, the way a checkpoint takes them: s_r = rint(a sqrt(n_r / n)),
+    hom_r = rint(b^2 / n + s_r^2 / n_r); (s_r, hom_r, largest |value - integer| met) over the checkpoints in use"""
+    a, b = np.asarray(a), np.asarray(b)
+    s_r = np.zeros(a.shape[:1] + (CP_CHECKPOINTS,), dtype=np.int64)
+    hom_r = np.zeros_like(s_r)
+    worst = 0.0
+    nn = np.float64(n)
+    for k, chunk in enumerate(chunks_list):
+        n_r = np.float64(n - CP_CHUNK_SAMPLES * chunk)
+        sv = a[:, k] * np.sqrt(n_r / nn)
+        s = np.rint(sv)
+        hv = (b[:, k] * b[:, k]) / nn + (s * s) / n_r
+        h = np.rint(hv)
+        worst = max(worst, float(np.abs(sv - s).max(initial=0.0)), float(np.abs(hv - h).max(initial=0.0)))
+        s_r[:, k], hom_r[:, k] = s.astype(np.int64), h.astype(np.int64)
+    return s_r, hom_r, worst
+
+
+CP_ROW_KINDS = ("random complete", "random 3% missing", "all missing", "all het", "monomorphic REF", "monomorphic ALT", "ALT-major with hets",
+                "exact tie", "complete but the last sample", "missing behind the last checkpoint", "missing before the first checkpoint",
+                "hom calls in one chunk before the first checkpoint", "hom calls in the last chunk", "60% missing", "random complete 2",
+                "random 3% missing ALT-major")
+
+
+def cp_test_rows(n, r2, count=16, seed=0):
+    """The rows tests/test_count_pass_slots.py feeds every count-pass form: (count, n) raw REF-based codes, one per CP_ROW_KINDS (the
+    first `count` of them), placed relative to checkpoint_chunks(n, r2)."""
+    rng = np.random.default_rng(1000003 * seed + n)
+    cps = checkpoint_chunks(n, r2)
+    n_chunks = (n + CP_CHUNK_SAMPLES - 1) // CP_CHUNK_SAMPLES
+    first = (cps[0] if cps else max(n_chunks - 1, 1)) * CP_CHUNK_SAMPLES     # samples in front of the first checkpoint
+    last = (cps[-1] if cps else max(n_chunks - 1, 1)) * CP_CHUNK_SAMPLES     # ... and of the last one
+    first, last = min(first, n - 1), min(last, n - 1)
+
+    def draw(maf):
+        return ((rng.random(n) < maf).astype(np.uint8) + (rng.random(n) < maf).astype(np.uint8)).astype(np.uint8)
+
+    rows = np.empty((len(CP_ROW_KINDS), n), dtype=np.uint8)
+    rows[0] = draw(0.3)
+    rows[1] = np.where(rng.random(n) < 0.03, 3, draw(0.2))
+    rows[2] = 3
+    rows[3] = 1
+    rows[4] = 0
+    rows[5] = 2
+    rows[6] = draw(0.8)
+    tie = np.ones(n, dtype=np.uint8)                 # as many REF as ALT alleles: ref_freq = 0.5 exactly, REF stays major
+    q = n // 4
+    tie[:q] = 0
+    tie[q:2 * q] = 2
+    rows[7] = rng.permutation(tie)
+    rows[8] = draw(0.4)
+    rows[8, n - 1] = 3
+    rows[9] = draw(0.7)
+    rows[9, last:] = np.where(rng.random(n - last) < 0.2, 3, rows[9, last:])
+    rows[9, n - 1] = 3
+    rows[10] = draw(0.35)
+    rows[10, :first] = np.where(rng.random(first) < 0.2, 3, rows[10, :first])
+    rows[10, 0] = 3
+    one = (first // CP_CHUNK_SAMPLES - 1) * CP_CHUNK_SAMPLES   # the chunk in front of the first checkpoint
+    rows[11] = 1
+    rows[11, one:one + CP_CHUNK_SAMPLES] = np.where(rng.random(CP_CHUNK_SAMPLES) < 0.7, 2, 0)[:n - one]
+    tail0 = (n_chunks - 1) * CP_CHUNK_SAMPLES
+    rows[12] = 1
+    rows[12, tail0:] = np.where(rng.random(n - tail0) < 0.3, 2, 0)
+    rows[13] = np.where(rng.random(n) < 0.6, 3, draw(0.25))
+    rows[14] = draw(0.05)
+    rows[15] = np.where(rng.random(n) < 0.03, 3, draw(0.9))
+    return np.ascontiguousarray(rows[:count])

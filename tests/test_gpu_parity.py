@@ -62,8 +62,9 @@ def test_prepare_planes_and_aggregates(gpu_pkg, n, encoding):
 
 @pytest.mark.parametrize("n", [40000, 200001, 500000, 1100003])
 def test_prepare_large_sample_counts(gpu_pkg, n):
-    """Every register-budget variant of prepare_kernel (rows of 1k .. 34k plane dwords), incl. 500k samples
-    (BASELINE configs 3-5) and the two-pass fallback above 1M samples."""
+    """Rows of 1k .. 34k plane dwords, incl. 500k samples (BASELINE configs 3-5) and the rolled loop above 1M samples.  With
+    today's defaults the engine keeps the code image, so the count pass under test is codes_kernel (128 x 7, 256 x 16, 512 x 16 and the
+    rolled 1024 x 0), not prepare_kernel as the name says; every form of both, checkpoint slots included: test_count_pass_slots.py."""
     pkg = gpu_pkg
     m = 6
     raw = T.synth_raw_codes(m, n, seed=n % 1000, missing_rate=0.03)
