@@ -301,6 +301,18 @@ int ldp_load_pgen_records(ldp_engine* e, uint32_t first_variant, uint32_t n, con
  * entries follow their rows through ldp_restrict_variants(); ldp_set_variants*() and ldp_release_device() clear them.  No device work:
  * the sums came back with the load's own synchronisation.  LDP_ERR_INVALID for a range beyond variant_ct. */
 int ldp_get_dosage_sums(ldp_engine* e, uint32_t first_variant, uint32_t n, uint64_t* ref_dosage, uint64_t* alt_dosage, uint8_t* has_sums);
+/* The allele counts ldp_load_pgen_records() chose the major allele of a variant with more than one ALT allele from, for variants
+ * [first_variant, +n) (the engine's current indices): the histogram the device builds while it collapses such a record -- one count per
+ * allele, 0 = REF, k = ALTk, two copies per called sample, over the file's samples or the samples of a plain-subset sample map (what
+ * --freq prints as ALT_FREQS / ALT_CTS / OBS_CT of the founders).  The caller lays the output out: offsets[q] .. offsets[q + 1] (n + 1
+ * nondecreasing entries) is variant first_variant + q's slot in counts[], as wide as its allele_ct.  has_counts[q] = 1 when the row of
+ * that variant was loaded by ldp_load_pgen_records() from a record whose allele_ct (> 2) equals the slot's width; counts then holds what
+ * counting ldp_pgen_read_alleles()'s pairs over the same samples gives.  has_counts[q] = 0 and a zeroed slot otherwise: one ALT allele
+ * (ldp_get_variant_recs has those counts), a variant this engine does not own, a row built by the host or loaded by any other call -- a
+ * later load of a row replaces its entry --, a slot of another width.  The entries follow their rows through ldp_restrict_variants();
+ * ldp_set_variants*() and ldp_release_device() clear them.  No device work: the counts came back with the copy that brings the major
+ * alleles.  LDP_ERR_INVALID for a range beyond variant_ct or decreasing offsets. */
+int ldp_get_allele_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint32_t* offsets, uint32_t* counts, uint8_t* has_counts);
 /* The same for --indep-pairphase (plink2_ld.cc:1449-2163; loader :2040-2052): the records' main tracks AND their hardcall-phase tracks
  * (auxiliary track 2, pgen_spec "Phased heterozygous hard-calls"; ReadGenovecHphaseSubsetUnsafe pgenlib_read.cc:6704, what
  * PgrGetInv1P :7016 hands HapsplitMustPhased pgenlib_misc.cc:1887) are decoded on the device into LDP_GENO_PHASED rows and loaded;

@@ -117,7 +117,7 @@ CABI_SYMBOLS = [
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
-    "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass",
+    "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass", "ldp_get_allele_counts",
 ]
 
 
@@ -176,7 +176,7 @@ def build_library(force=False, verbose=False, measure=False):
 def cli_sources():
     """the front-end's translation units: main() + one unit per concern (csrc/p2h_cli.h is what they share)"""
     return [os.path.join(CSRC, f) for f in ("plink2_hip_cli.cpp", "p2h_util.cpp", "p2h_args.cpp", "p2h_tables.cpp", "p2h_inputs.cpp", "p2h_clump.cpp", "p2h_r2.cpp",
-                                            "p2h_r2_phased.cpp", "p2h_prune.cpp")]
+                                            "p2h_r2_phased.cpp", "p2h_prune.cpp", "p2h_reports.cpp")]
 
 
 def build_cli(force=False, verbose=False):
@@ -270,6 +270,7 @@ def lib():
     L.ldp_get_variant_recs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp]
     L.ldp_get_maj_freqs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, f64p]
     L.ldp_get_dosage_sums.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p, ctypes.POINTER(ctypes.c_uint8)]
+    L.ldp_get_allele_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint8)]
     L.ldp_get_planes.argtypes = [vp, ctypes.c_uint32, u32p, u32p]
     L.ldp_get_counters.argtypes = [vp, ctypes.POINTER(ldp_counters)]
     L.ldp_synth_genotypes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, vp,
@@ -1046,6 +1047,18 @@ class LdPruneEngine:
         has = np.zeros(max(n, 1), dtype=np.uint8)
         self._ck(self._L.ldp_get_dosage_sums(self._h, first, n, _ptr(ref, ctypes.c_uint64), _ptr(alt, ctypes.c_uint64), _ptr(has, ctypes.c_uint8)))
         return ref[:n], alt[:n], has[:n]
+
+    def allele_counts(self, allele_cts, first=0):
+        """(counts, has): per variant of [first, first + len(allele_cts)) the allele counts the device collapsed a multiallelic record with --
+        a list of uint32 arrays, allele_cts[q] entries each -- and has[q] = 1 where the row has them (ldp_get_allele_counts)."""
+        allele_cts = np.asarray(allele_cts, dtype=np.uint32)
+        n = int(allele_cts.size)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum(allele_cts)
+        counts = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        has = np.zeros(max(n, 1), dtype=np.uint8)
+        self._ck(self._L.ldp_get_allele_counts(self._h, first, n, _ptr(off, ctypes.c_uint32), _ptr(counts, ctypes.c_uint32), _ptr(has, ctypes.c_uint8)))
+        return [counts[off[q]:off[q + 1]].copy() for q in range(n)], has[:n]
 
     def planes(self, variant):
         w = (self.founder_ct + 31) // 32

@@ -448,7 +448,11 @@ struct PgenDecodeArgs {
   uint32_t n_multi;
   double* maj_freq;             // out, per entry of multi_rec: GetAlleleFreq of the major allele
   uint32_t* maj_idx;            // out: the major allele
-  uint8_t* row_inverse;         // out, per RECORD: 1 = the row now counts copies of non-major alleles (LDP_GENO_INVERSE)
+  // ... and the allele counts the choice was made from (ldp_get_allele_counts): allele a of entry m at allele_cts[allele_off[m] + a],
+  // a < its allele_ct, over the samples of sample_mask; allele_cts NULL = not wanted
+  const uint32_t* allele_off;   // per entry of multi_rec: prefix sums of the entries' allele_ct
+  uint32_t* allele_cts;
+  uint8_t* row_inverse;        // out, per RECORD: 1 = the row now counts copies of non-major alleles (LDP_GENO_INVERSE)
   const uint32_t* sample_mask;  // optional bitmap over the file's samples: the ones whose alleles count (a subset sample map: the founders)
   uint32_t mask_ct;             // ... and how many they are
   // --indep-pairphase: the hardcall-phase track decoded into the rows' second part (LDP_GENO_PHASED layout); 0 = not wanted

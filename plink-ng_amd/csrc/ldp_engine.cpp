@@ -147,6 +147,11 @@ void free_device(ldp_engine* e, bool keep_image) {
       e->h_dec_pin = nullptr;
       e->dec_pin_cap = 0;
     }
+    if (e->h_ac_pin) {
+      (void)hipHostFree(e->h_ac_pin);
+      e->h_ac_pin = nullptr;
+      e->ac_pin_cap = 0;
+    }
     (void)hipFree(e->d_sample_map);
     (void)hipFree(e->d_gather);
     (void)hipFree(e->d_extra_het);
@@ -941,6 +946,7 @@ void build_shard(ldp_engine* e) {
   e->dos_ref.assign(local, 0);
   e->dos_alt.assign(local, 0);
   e->dos_has.assign(local, 0);
+  e->allele_cts.assign(local, std::vector<uint32_t>());
   e->loaded_special = false;
 }
 
@@ -1590,6 +1596,7 @@ int ldp_release_device(ldp_engine* e) {
   std::fill(e->loaded.begin(), e->loaded.end(), 0);
   std::fill(e->load_tag.begin(), e->load_tag.end(), 0);
   std::fill(e->dos_has.begin(), e->dos_has.end(), 0);
+  e->allele_cts.assign(e->allele_cts.size(), std::vector<uint32_t>());
   for (uint8_t& m : e->mf_set) {
     m = (m == 1) ? 1 : 0;  // (caller-supplied frequencies stay)
   }
@@ -2003,6 +2010,31 @@ int ldp_get_dosage_sums(ldp_engine* e, uint32_t first_variant, uint32_t n, uint6
     has_sums[q] = has ? 1 : 0;
     ref_dosage[q] = has ? e->dos_ref[l] : 0;
     alt_dosage[q] = has ? e->dos_alt[l] : 0;
+  }
+  return LDP_OK;
+}
+
+int ldp_get_allele_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint32_t* offsets, uint32_t* counts, uint8_t* has_counts) {
+  if (!e || !e->planned) {
+    return e ? fail(e, LDP_ERR_STATE, "ldp_set_variants() first") : LDP_ERR_INVALID;
+  }
+  if ((static_cast<uint64_t>(first_variant) + n > e->variant_ct) || (n && (!offsets || !counts || !has_counts))) {
+    return fail(e, LDP_ERR_INVALID, "variant range out of bounds / null pointer");
+  }
+  for (uint32_t q = 0; q < n; ++q) {
+    if (offsets[q + 1] < offsets[q]) {
+      return fail(e, LDP_ERR_INVALID, "offsets must be nondecreasing");
+    }
+  }
+  for (uint32_t q = 0; q < n; ++q) {
+    const int64_t l = e->global_to_local[first_variant + q];
+    const uint32_t want = offsets[q + 1] - offsets[q];
+    // (a row whose slot is narrower or wider than the record's allele count was loaded with another allele_ct than the caller expects: no counts)
+    const bool has = (l >= 0) && e->loaded[l] && (!e->allele_cts[l].empty()) && (e->allele_cts[l].size() == want);
+    has_counts[q] = has ? 1 : 0;
+    for (uint32_t a = 0; a < want; ++a) {
+      counts[offsets[q] + a] = has ? e->allele_cts[l][a] : 0;
+    }
   }
   return LDP_OK;
 }

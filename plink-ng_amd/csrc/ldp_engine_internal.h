@@ -305,6 +305,9 @@ struct ldp_engine {
   // the allele dosage sums the device computed while it decoded a row's record (pgen_dosage_kernel; ldp_get_dosage_sums)
   std::vector<uint64_t> dos_ref, dos_alt;  // local
   std::vector<uint8_t> dos_has;            // local: 1 = the two above are set for the row as it is loaded now
+  // the allele counts pgen_aux1_kernel chose a multiallelic row's major allele from (ldp_get_allele_counts): allele_ct entries, empty = the row
+  // as it is loaded now has none (one ALT allele, or built by the host)
+  std::vector<std::vector<uint32_t>> allele_cts;  // local
   bool loaded_special = false;            // some row came as LDP_GENO_PHASED or through a sample map that is no plain subset: a count of the image row alone
                                           // would not give its record again (ldp_restrict_variants refuses such engines)
 
@@ -396,6 +399,8 @@ struct ldp_engine {
   } dec;
   uint8_t* h_dec_pin = nullptr;  // pinned: the launch's descriptors going up, its per-record results coming down (pageable copies cost ~0.2 ms each)
   size_t dec_pin_cap = 0;
+  uint32_t* h_ac_pin = nullptr;  // pinned, launches with multiallelic records: allele-count offsets going up | major alleles and allele counts coming down
+  size_t ac_pin_cap = 0;         // (dwords)
   uint8_t* d_ld_base = nullptr;
   size_t ld_base_cap = 0;
   bool ld_base_valid = false;

@@ -305,6 +305,7 @@ int load_rows_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, const void
       std::fill(e->loaded.begin() + l0, e->loaded.begin() + l0 + cnt, static_cast<uint8_t>(1));
       std::fill(e->load_tag.begin() + l0, e->load_tag.begin() + l0 + cnt, e->load_epoch);
       std::fill(e->dos_has.begin() + l0, e->dos_has.begin() + l0 + cnt, static_cast<uint8_t>(0));  // (ldp_load_pgen_records sets them again behind this call)
+      std::fill(e->allele_cts.begin() + l0, e->allele_cts.begin() + l0 + cnt, std::vector<uint32_t>());  // (... and these)
       // (what ldp_restrict_variants() needs to count the rows again where they lie)
       if (!h_row_inverse) {
         std::fill(e->row_inv_loaded.begin() + l0, e->row_inv_loaded.begin() + l0 + cnt, static_cast<uint8_t>(base_encoding == LDP_GENO_INVERSE));
@@ -514,8 +515,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
   double* h_maj_freq = reinterpret_cast<double*>(e->h_dec_pin + rows_cap * sizeof(ldp::PgenRecDesc));
   uint64_t* h_sums = reinterpret_cast<uint64_t*>(h_maj_freq + rows_cap);
   uint32_t* h_multi = reinterpret_cast<uint32_t*>(h_sums + 2 * rows_cap);
-  uint32_t* h_maj_idx = h_multi + rows_cap;
-  uint32_t* h_dos = h_maj_idx + rows_cap;
+  uint32_t* h_dos = h_multi + 2 * rows_cap;  // (the rows_cap dwords in between held the major alleles before they came down with the allele counts: h_ac_pin)
   int* h_err_pin = reinterpret_cast<int*>(h_dos + rows_cap);
   for (uint32_t q0 = 0; (q0 < n) && (status == LDP_OK); q0 += rows_per_launch) {
     const double t_call = now_ms();
@@ -527,6 +527,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     }
     multi.clear();
     dos.clear();
+    size_t allele_total = 0;  // alleles of this launch's multiallelic records: one count each comes back (ldp_get_allele_counts)
     uint32_t last_alone = with_base_rec ? cnt : (have_carried ? kPgenBaseCarried : kPgenNoBase);
     int64_t last_alone_row = -1;
     for (uint32_t q = 0; q < cnt; ++q) {
@@ -549,6 +550,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       }
       if (r.allele_ct > 2) {
         multi.push_back(q);
+        allele_total += r.allele_ct;
       } else if (want_sums && (r.vrtype & 0x60u) && (e->global_to_local[first_variant + q0 + q] >= 0)) {
         dos.push_back(q);  // (the reference has no sums for a record with several ALT alleles either: pgenlib_read.cc:8036)
       }
@@ -611,6 +613,7 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
       // (a malformed record, a failed copy, launch or sync) -- until load_rows_impl has counted them again
       std::fill(e->loaded.begin() + l_first, e->loaded.begin() + l_first + cnt, static_cast<uint8_t>(0));
       std::fill(e->dos_has.begin() + l_first, e->dos_has.begin() + l_first + cnt, static_cast<uint8_t>(0));
+      std::fill(e->allele_cts.begin() + l_first, e->allele_cts.begin() + l_first + cnt, std::vector<uint32_t>());
       if (e->d_stored_inv) {
         HIP_TRY(e, hipMemsetAsync(e->d_stored_inv + l_first, 0, cnt, e->stream));  // (... and they will be in the file's orientation)
       }
@@ -619,18 +622,43 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     void *p_recs = nullptr, *p_rows = nullptr, *p_end = nullptr, *p_multi = nullptr, *p_mf = nullptr, *p_mi = nullptr, *p_inv = nullptr, *p_dos = nullptr, *p_sums = nullptr;
     if ((rc = dec_reserve(e, 1, rows * sizeof(ldp::PgenRecDesc), &p_recs)) ||
         (into_image ? 0 : (rc = dec_reserve(e, 2, static_cast<size_t>(rows) * stride, &p_rows))) ||
-        (rc = dec_reserve(e, 3, rows * sizeof(uint64_t), &p_end)) || (rc = dec_reserve(e, 4, (multi.size() + 1) * sizeof(uint32_t), &p_multi)) ||
-        (rc = dec_reserve(e, 5, (multi.size() + 1) * sizeof(double), &p_mf)) || (rc = dec_reserve(e, 6, (multi.size() + 1) * sizeof(uint32_t) + sizeof(int), &p_mi)) ||
+        (rc = dec_reserve(e, 3, rows * sizeof(uint64_t), &p_end)) || (rc = dec_reserve(e, 4, 2 * (multi.size() + 1) * sizeof(uint32_t), &p_multi)) ||
+        (rc = dec_reserve(e, 5, (multi.size() + 1) * sizeof(double), &p_mf)) || (rc = dec_reserve(e, 6, (multi.size() + 1 + allele_total) * sizeof(uint32_t) + sizeof(int), &p_mi)) ||
         (rc = dec_reserve(e, 7, rows + 8, &p_inv)) || (rc = dec_reserve(e, 8, (dos.size() + 1) * sizeof(uint32_t), &p_dos)) ||
         (rc = dec_reserve(e, 9, (dos.size() + 1) * 2 * sizeof(uint64_t), &p_sums))) {
       return rc;
     }
-    int* d_err = reinterpret_cast<int*>(static_cast<uint32_t*>(p_mi) + multi.size() + 1);
+    // slot 4: record indices | allele-count offsets; slot 6: major alleles | allele counts | the error word
+    uint32_t* d_allele_off = static_cast<uint32_t*>(p_multi) + multi.size() + 1;
+    uint32_t* d_allele_cts = static_cast<uint32_t*>(p_mi) + multi.size() + 1;
+    int* d_err = reinterpret_cast<int*>(d_allele_cts + allele_total);
+    uint32_t* h_allele_off = nullptr;  // multi.size() + 1 prefix sums
+    uint32_t* h_maj_idx = nullptr;     // multi.size() + 1 dwords, then the allele counts as the device laid them out
+    if (!multi.empty()) {
+      const size_t want = 2 * (multi.size() + 1) + allele_total;
+      if (e->ac_pin_cap < want) {
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (e->h_ac_pin) {
+          (void)hipHostFree(e->h_ac_pin);
+          e->h_ac_pin = nullptr;
+          e->ac_pin_cap = 0;
+        }
+        HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_ac_pin), (want + want / 4) * sizeof(uint32_t), hipHostMallocDefault));
+        e->ac_pin_cap = want + want / 4;
+      }
+      h_allele_off = e->h_ac_pin;
+      h_maj_idx = e->h_ac_pin + multi.size() + 1;
+      h_allele_off[0] = 0;
+      for (size_t k = 0; k < multi.size(); ++k) {
+        h_allele_off[k + 1] = h_allele_off[k] + descs[multi[k]].allele_ct;
+      }
+    }
     uint32_t* d_unphased = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(p_inv) + ((static_cast<size_t>(rows) + 3) & ~static_cast<size_t>(3)));  // (behind the row flags)
     HIP_TRY(e, hipMemcpyAsync(p_recs, descs, rows * sizeof(ldp::PgenRecDesc), hipMemcpyHostToDevice, e->stream));
     if (!multi.empty()) {
       memcpy(h_multi, multi.data(), multi.size() * sizeof(uint32_t));
       HIP_TRY(e, hipMemcpyAsync(p_multi, h_multi, multi.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(d_allele_off, h_allele_off, (multi.size() + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     }
     if (!dos.empty()) {
       memcpy(h_dos, dos.data(), dos.size() * sizeof(uint32_t));
@@ -656,6 +684,8 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     DA.n_multi = static_cast<uint32_t>(multi.size());
     DA.maj_freq = static_cast<double*>(p_mf);
     DA.maj_idx = static_cast<uint32_t*>(p_mi);
+    DA.allele_off = d_allele_off;
+    DA.allele_cts = multi.empty() ? nullptr : d_allele_cts;
     DA.row_inverse = static_cast<uint8_t*>(p_inv);
     if (mapped && e->map_is_subset && (!e->d_map_mask) && ((!multi.empty()) || !dos.empty())) {
       // (the device copy went with a re-plan or ldp_release_device(): the host's sample map is the master)
@@ -713,7 +743,8 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     }
     if (!multi.empty()) {
       HIP_TRY(e, hipMemcpyAsync(h_maj_freq, p_mf, multi.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(e, hipMemcpyAsync(h_maj_idx, p_mi, multi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+      // (the major alleles and, behind them in the same buffer, the allele counts they were chosen from: one copy)
+      HIP_TRY(e, hipMemcpyAsync(h_maj_idx, p_mi, (multi.size() + 1 + allele_total) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     }
     if (!dos.empty()) {
       HIP_TRY(e, hipMemcpyAsync(h_sums, p_sums, dos.size() * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
@@ -762,6 +793,8 @@ int load_pgen_records_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
         if (l >= 0) {
           e->maj_freq[l] = h_maj_freq[k];
           e->mf_set[l] = 1;
+          const uint32_t* cts = h_maj_idx + multi.size() + 1 + h_allele_off[k];
+          e->allele_cts[l].assign(cts, cts + (h_allele_off[k + 1] - h_allele_off[k]));
         }
       }
       for (size_t k = 0; k < dos.size(); ++k) {

@@ -99,11 +99,13 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
   std::vector<uint8_t> new_mf_set(new_local), new_inv(new_local);
   std::vector<uint64_t> new_dos_ref(new_local), new_dos_alt(new_local);
   std::vector<uint8_t> new_dos_has(new_local);
+  std::vector<std::vector<uint32_t>> new_allele_cts(new_local);
   bool any_inv = false;
   for (uint32_t k = 0; k < new_local; ++k) {
     new_dos_ref[k] = e->dos_ref[src[k]];
     new_dos_alt[k] = e->dos_alt[src[k]];
     new_dos_has[k] = e->dos_has[src[k]];
+    new_allele_cts[k] = e->allele_cts[src[k]];
     new_mf[k] = e->maj_freq[src[k]];
     new_mf_set[k] = e->mf_set[src[k]];
     new_inv[k] = e->row_inv_loaded[src[k]];
@@ -284,6 +286,7 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
   e->dos_ref.swap(new_dos_ref);
   e->dos_alt.swap(new_dos_alt);
   e->dos_has.swap(new_dos_has);
+  e->allele_cts.swap(new_allele_cts);  // (... and so do a multiallelic row's allele counts)
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // (the temporaries above are read until here)
   return LDP_OK;
 }

@@ -828,6 +828,12 @@ __global__ __launch_bounds__(kAuxThreads) void pgen_aux1_kernel(PgenDecodeArgs A
     }
     return;
   }
+  if (A.allele_cts && (tid < allele_ct)) {
+    // the histogram itself, for the reports that print it (--freq): REF and ALT1 from the main track's genotype counts and the patches'
+    // deltas, the others straight from the patches -- the same numbers count_of() below turns into frequencies
+    const uint32_t c = (tid == 0) ? (2u * f0 + f1) : ((tid == 1) ? static_cast<uint32_t>(static_cast<int>(f1 + 2u * f2) + s_cnt[1]) : static_cast<uint32_t>(s_cnt[tid]));
+    A.allele_cts[A.allele_off[m] + tid] = c;
+  }
   if (tid == 0) {
     // ComputeAlleleFreqs (plink2_filter.cc:2113-2153): freq[a] = count[a] * (1 / total) for all alleles but the last, 1 / k each
     // when nothing is observed; GetMajIdxMulti (plink2_common.cc:1042-1070); GetAlleleFreq (plink2_common.h:584-593)

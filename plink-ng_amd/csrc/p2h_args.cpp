@@ -807,6 +807,65 @@ bool parse_misc_flags(Args& A, ArgCursor& c, const std::string& f) {
   return true;
 }
 
+// the count reports: --missing (plink2.cc:8600-8665), --freq (:6122-6197), --geno-counts (:6515-6550).  Default columns only: every other
+// modifier the reference knows is refused by name (exit 63); what the reference rejects is rejected with its message (exit 8)
+bool parse_report_flags(Args& A, ArgCursor& c, const std::string& f) {
+  LDP_ARG_FAMILY_PROLOGUE;
+  if ((f != "--missing") && (f != "--freq") && (f != "--geno-counts") && (f != "--nonfounders")) {
+    return false;
+  }
+  if (f == "--nonfounders") {
+    die(63, "Error: --nonfounders is not supported by plink2-hip: --freq counts founders only.\n");
+  }
+  const uint32_t max_params = (f == "--missing") ? 4 : ((f == "--freq") ? 5 : 2);
+  std::vector<std::string> mods;
+  while ((i + 1 < argc) && (argv[i + 1][0] != '-')) {
+    mods.push_back(argv[++i]);
+  }
+  if (mods.size() > max_params) {  // EnforceParamCtRange (plink2_cmdline.cc)
+    die(8, "Error: %s accepts at most %u arguments.\n", f.c_str(), max_params);
+  }
+  auto starts = [](const std::string& s, const char* prefix) { return s.compare(0, strlen(prefix), prefix) == 0; };
+  auto unsupported = [&](const std::string& m) { die(63, "Error: the '%s' modifier of %s is not supported by plink2-hip (default columns, 'zs'%s only).\n", m.c_str(), f.c_str(),
+                                                     (f == "--missing") ? ", 'sample-only', 'variant-only'" : ((f == "--freq") ? ", 'counts'" : "")); };
+  for (const std::string& m : mods) {
+    if (f == "--missing") {
+      if (m == "zs") {
+        A.rep_missing_zs = true;
+      } else if ((m == "sample-only") || (m == "variant-only")) {
+        if ((m == "sample-only") ? A.rep_variant_only : A.rep_sample_only) {
+          die(8, "Error: --missing 'sample-only' and 'variant-only' cannot be used together.\n");
+        }
+        ((m == "sample-only") ? A.rep_sample_only : A.rep_variant_only) = true;
+      } else if (starts(m, "scols=") || starts(m, "vcols=")) {
+        unsupported(m);
+      } else {
+        die(8, "Error: Invalid --missing argument '%s'.\n", m.c_str());
+      }
+    } else if (f == "--freq") {
+      if (m == "zs") {
+        A.rep_freq_zs = true;
+      } else if (m == "counts") {
+        A.rep_freq_counts = true;
+      } else if ((m == "case-control") || starts(m, "cols=") || (m == "bins-only") || starts(m, "refbins=") || starts(m, "refbins-file=") || starts(m, "alt1bins=") || starts(m, "alt1bins-file=")) {
+        unsupported(m);
+      } else {
+        die(8, "Error: Invalid --freq argument '%s'.\n", m.c_str());
+      }
+    } else {
+      if (m == "zs") {
+        A.rep_gcount_zs = true;
+      } else if (starts(m, "cols=")) {
+        unsupported(m);
+      } else {
+        die(8, "Error: Invalid --geno-counts argument '%s'.\n", m.c_str());
+      }
+    }
+  }
+  ((f == "--missing") ? A.rep_missing : ((f == "--freq") ? A.rep_freq : A.rep_gcount)) = true;
+  return true;
+}
+
 #undef LDP_ARG_FAMILY_PROLOGUE
 
 // what the reference checks between flags once all of them are read
@@ -828,7 +887,7 @@ void check_flag_combinations(Args& A) {
   } else if (A.clump_unphased) {
     die(8, "Error: --clump-unphased must be used with --clump.\n");
   }
-  if (!A.have_prune && !A.have_r2) {
+  if (!A.have_prune && !A.have_r2 && !A.any_report()) {
     die(8, "Error: no command given (plink2-hip implements --indep-pairwise and --r2-unphased matrices).\n");
   }
   if (A.have_prune && (A.parallel_tot != 1)) {
@@ -926,7 +985,7 @@ Args parse_args(int argc, char** argv) {
   for (; c.i < argc; ++c.i) {
     const std::string f = argv[c.i];
     if (!(parse_input_flags(A, c, f) || parse_command_flags(A, c, f) || parse_clump_flags(A, c, f) || parse_filter_flags(A, c, f) || parse_ldwindow_flags(A, c, f) ||
-          parse_misc_flags(A, c, f))) {
+          parse_report_flags(A, c, f) || parse_misc_flags(A, c, f))) {
       die(8, "Error: Unrecognized flag ('%s').  plink2-hip implements the --indep-pairwise path only.\n", f.c_str());
     }
   }

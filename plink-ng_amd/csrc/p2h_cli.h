@@ -210,6 +210,13 @@ struct Args {
   double clump_r2_raw = 0.5;
   double clump_r2 = 0.5 * (1.0 + kSmallEpsilon);
   uint32_t clump_bp_radius = 249999;
+  // the count reports (p2h_reports.cpp): --missing ['zs'] ['sample-only' | 'variant-only'], --freq ['zs'] ['counts'], --geno-counts ['zs']
+  bool rep_missing = false, rep_missing_zs = false, rep_sample_only = false, rep_variant_only = false;
+  bool rep_freq = false, rep_freq_zs = false, rep_freq_counts = false;
+  bool rep_gcount = false, rep_gcount_zs = false;
+  bool any_report() const { return rep_missing || rep_freq || rep_gcount; }
+  bool rep_smiss() const { return rep_missing && !rep_variant_only; }
+  bool rep_vmiss() const { return rep_missing && !rep_sample_only; }
   bool timing = false;    // --timing: print per-phase wall times
   bool dry_run = false;  // parse + plan only, print the parameters exactly (%a) and exit: used by the CPU tests
 };
@@ -488,6 +495,7 @@ struct XWeighted {
 };
 
 int chrom_code(const std::string& name_in);
+bool chrom_listed(const std::vector<std::string>& terms, const std::string& name);
 // what --clump needs to know about sex chromosomes (ClumpReports :8150-8215, :8460-8482)
 struct ClumpSex {
   const std::vector<uint8_t>* vcls = nullptr;  // per included variant: 3 chrX, 4 chrY
@@ -553,6 +561,11 @@ struct Session {
   std::vector<std::string> sample_keys;  // "FID<tab>IID" per sample of the file (kept for <out>.mindrem.id)
   std::vector<std::string> sample_sids;  // SID per sample when the .psam has the column
   bool fid_present = true;
+  // the count reports: from the device's records after the load (report_device; device_filter is set with it, as for mind_device), or from the host's
+  // pass in load_inputs(), which says why; report_variants: what the reports list (== inc[] when run_prune() writes them)
+  bool report_device = false;
+  const char* report_host_reason = nullptr;
+  std::vector<uint32_t> report_variants;
   double t_begin_first = 0.0;            // restarted run: main()'s first start (the total of --timing covers both loads)
   // (... and, once the runtime is up, this thread -- the one that creates the engines, their copy threads and their pinned staging -- moves next to the device)
   void join_hip() {
@@ -602,6 +615,27 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
 uint32_t mind_decide(const Session& S, const std::vector<uint32_t>& missing_cts, std::vector<uint8_t>* removed);
 // ... applied: the removed samples are neither kept nor founders from here on; exit 13 when nobody is left (plink2.cc:1836-1838)
 void mind_apply(Session& S, const std::vector<uint8_t>& removed);
+
+// ---- the count reports (p2h_reports.cpp): --missing (.smiss, .vmiss), --freq (.afreq, .acount), --geno-counts (.gcount) ----
+// What the one writer takes, whichever pass counted: the host's over the rows (load_inputs) or the device's count pass (run_prune).
+struct ReportCounts {
+  std::vector<uint32_t> variants;          // raw index of every listed variant: what the table filters leave, chromosome 0 included
+  std::vector<uint32_t> missing;           // per listed variant: missing calls among the kept samples
+  std::vector<uint32_t> f_ref2, f_het, f_alt2;  // ... the founders' genotype counts (--freq; meaningless for a variant with several ALT alleles)
+  std::vector<uint32_t> s_ref2, s_het, s_alt2;  // ... the kept samples' (--geno-counts); empty: the same samples, the same counts
+  std::unordered_map<uint32_t, std::vector<uint32_t>> allele_cts;  // listed variant with several ALT alleles -> the founders' count of every allele
+  std::vector<uint32_t> sample_missing;    // per sample of the file (kept samples only are read): missing calls over the listed variants
+  uint32_t kept_sample_ct = 0;
+};
+// the variants the reports list; refuses (exit 63) what the reports do not cover: chrX / chrY / MT, dosage tracks, a phenotype for .smiss, --geno-counts
+// with a variant that has several ALT alleles
+void reports_list_variants(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids,
+                           std::vector<uint32_t>* listed);
+// the founders' allele counts of a listed variant with several ALT alleles, from the reader's allele pairs (ldp_pgen_read_alleles): the host
+// pass's source, and the device pass's for rows the host built
+void reports_count_alleles_host(const Session& S, uint32_t raw_variant, std::vector<uint8_t>* lo, std::vector<uint8_t>* hi, std::vector<uint32_t>* counts);
+// the files and their log lines, in the reference's order
+void write_reports(const Session& S, const ReportCounts& C);
 
 void load_inputs(Session& S, int argc, char** argv);
 int run_r2(Session& S);

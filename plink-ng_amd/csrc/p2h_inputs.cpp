@@ -275,7 +275,7 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
   if (g_dbg.host_filter) {
     return "--debug-host-filter";
   }
-  if ((!A.have_prune) || A.pairphase) {
+  if (((!A.have_prune) && (A.have_r2 || !A.any_report())) || A.pairphase) {  // (a run of reports alone loads like the prune)
     return A.pairphase ? "--indep-pairphase plans its engines before the load" : "the r^2 outputs and --clump plan their engines before the load";
   }
   if (A.gpus != 1) {
@@ -481,6 +481,112 @@ static void sample_filter_mind(Session& S, bool chr_filter, const std::unordered
   }
 }
 
+// The reports' stage of load_inputs(): what they list, then either the decision that run_prune() writes them from the engine's records
+// (S.report_device: the same conditions as for the count filters, device_filter_refusal) or the host's pass -- count_rows over a founder mask
+// and a kept-sample mask, the per-sample pass --mind has, ldp_pgen_read_alleles for a variant with several ALT alleles -- and the writer.
+static void reports_stage(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+  const Args& A = S.A;
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  reports_list_variants(S, chr_filter, extract_ids, exclude_ids, &S.report_variants);
+  const std::vector<uint32_t>& todo = S.report_variants;
+  if (todo.empty()) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
+    die(13, "Error: No variants remaining after main filters.\n");
+  }
+  const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
+  std::vector<uint64_t> m_f(words, 0), m_s(words, 0);
+  uint32_t kept_samples = 0, founders = 0;
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    if (S.sample_kept.empty() || S.sample_kept[sx]) {
+      m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
+      ++kept_samples;
+    }
+    if (S.is_founder[sx]) {
+      m_f[sx >> 5] |= 1ull << (2 * (sx & 31));
+      ++founders;
+    }
+  }
+  if (A.rep_freq && A.rep_freq_counts && (kept_samples != founders) && !A.ac_founders) {  // plink2.cc:2102-2105
+    die(7, "Error: --mac/--max-mac/\"--freq counts\" specified, but with neither\n--ac-founders nor --nonfounders; and nonfounders are present.\n");
+  }
+  const char* reason = device_filter_refusal(A, false, kept_samples, founders);
+  if (!reason) {
+    reason = A.dry_run ? "--dry-run"
+             : ((founders < 2) ? "fewer than two founders (no engine)"
+             : ((A.rep_smiss() && (founders > ldp_matrix_pipe_max_founders())) ? "more founders than the resident 2-bit image takes (the per-sample counts are read off it)" : nullptr));
+  }
+  if (A.dry_run) {
+    logprintf("dry-run: reports: %s%s\n", reason ? "host pass: " : "from the device's count pass", reason ? reason : "");
+  }
+  if (!reason) {
+    S.report_device = true;
+    return;
+  }
+  S.report_host_reason = reason;
+  const double t0 = now_s();
+  int storage_mode = 0;
+  ldp_pgen_info(S.pg, nullptr, nullptr, &storage_mode, nullptr, nullptr);
+  const bool bed = (storage_mode == 0x01);
+  uint64_t rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
+  const uint8_t* direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(S.pg, &rec_bytes));  // NULL for variable-width
+  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  const bool two_sets = (kept_samples != founders) && A.rep_gcount;  // (--geno-counts counts every kept sample, --freq the founders)
+  std::vector<RowCounts> fc(todo.size()), sc(two_sets ? todo.size() : 0);
+  std::vector<std::vector<uint32_t>> part(A.rep_smiss() ? nthreads : 0, std::vector<uint32_t>(32 * words, 0));  // (per thread; summed below)
+  for_each_row_run(S.pg, S.gpath, direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t q) {
+    count_rows(rows, rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &fc[q]);
+    if (two_sets) {
+      count_rows(rows, rec_bytes, n, bed, raw_sample_ct, m_s, m_s, &sc[q]);
+    }
+    if (!part.empty()) {
+      count_sample_missing(rows, rec_bytes, n, bed, raw_sample_ct, m_s, part[t].data());
+    }
+  });
+  ReportCounts C;
+  C.variants = todo;
+  C.kept_sample_ct = kept_samples;
+  C.missing.resize(todo.size());
+  C.f_ref2.resize(todo.size());
+  C.f_het.resize(todo.size());
+  C.f_alt2.resize(todo.size());
+  for (size_t q = 0; q < todo.size(); ++q) {
+    C.missing[q] = fc[q].missing;
+    C.f_ref2[q] = fc[q].ref2;
+    C.f_het[q] = fc[q].het;
+    C.f_alt2[q] = fc[q].alt2;
+  }
+  if (two_sets) {
+    C.s_ref2.resize(todo.size());
+    C.s_het.resize(todo.size());
+    C.s_alt2.resize(todo.size());
+    for (size_t q = 0; q < todo.size(); ++q) {
+      C.s_ref2[q] = sc[q].ref2;
+      C.s_het[q] = sc[q].het;
+      C.s_alt2[q] = sc[q].alt2;
+    }
+  }
+  if (A.rep_freq) {
+    std::vector<uint8_t> lo, hi;
+    for (size_t q = 0; q < todo.size(); ++q) {
+      if (S.V.alt_ct[todo[q]] > 1) {
+        reports_count_alleles_host(S, todo[q], &lo, &hi, &C.allele_cts[static_cast<uint32_t>(q)]);
+      }
+    }
+  }
+  C.sample_missing.assign(raw_sample_ct, 0);
+  for (const std::vector<uint32_t>& p : part) {
+    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+      C.sample_missing[sx] += p[sx];
+    }
+  }
+  const bool muted = g_log_mute;  // (a run that --mind started over logs nothing twice; these lines are this load's own)
+  g_log_mute = false;
+  write_reports(S, C);
+  g_log_mute = muted;
+  if (A.timing) {
+    logprintf("[timing] reports: host pass (%.3f s; %s)\n", now_s() - t0, reason);
+  }
+}
+
 void load_inputs(Session& S, int argc, char** argv) {
   S.t_begin = S.t_begin_first ? S.t_begin_first : now_s();
   S.A = parse_args(argc, argv);
@@ -512,7 +618,7 @@ void load_inputs(Session& S, int argc, char** argv) {
   const bool sample_filter = (!A.keep_files.empty()) || (!A.remove_files.empty());
   const bool mind_on = (A.mind < 1.0);  // plink2.cc:8910
   std::vector<std::pair<std::string, std::string>> parent_keys;
-  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
+  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on || A.rep_smiss()) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
                &S.sample_sids);
   // --make-founders (MakeFounders, plink2_filter.cc:4372-4443): a non-founder with a parent (both, with 'require-2-missing') that
   // is not among the samples in play becomes a founder; 'first' applies it before --keep / --remove, else after them
@@ -645,7 +751,7 @@ void load_inputs(Session& S, int argc, char** argv) {
     }
     die(13, "Error: This run estimates linkage disequilibrium between variants, but there\nare less than 50 founders to estimate from.  --make-founders may help.\n(Strictly speaking, you can also override this error with --bad-ld, but this is\nalmost always a bad idea.)\n");
   }
-  if (founder_ct < 2) {
+  if ((founder_ct < 2) && (A.have_prune || A.have_r2)) {
     die(7, "Error: %s requires at least two founders. (--make-founders may come in handy here.)\n", A.have_prune ? (A.pairphase ? "--indep-pairphase" : "--indep-pairwise") : "--r2-unphased");
   }
 
@@ -693,7 +799,12 @@ void load_inputs(Session& S, int argc, char** argv) {
       die(7, "Error: --mac/--max-mac/\"--freq counts\" specified, but with neither\n--ac-founders nor --nonfounders; and nonfounders are present.\n");
     }
   }
-  if (freq_filter || (A.geno != 1.0)) {
+  // ---- the count reports: after the sample filters, before --geno / --maf / --mac (plink2.cc:2370-2470)
+  if (A.any_report()) {
+    reports_stage(S, chr_filter, extract_ids, exclude_ids);
+  }
+  // (a run of reports alone: nothing reads the filtered variant list, and the reference applies no variant filter then)
+  if ((freq_filter || (A.geno != 1.0)) && (A.have_prune || A.have_r2)) {
     std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome
     std::vector<uint32_t> todo;
     for (uint32_t v = 0; v < raw_variant_ct; ++v) {
@@ -776,6 +887,10 @@ void load_inputs(Session& S, int argc, char** argv) {
         logprintf("[timing] variant filters: host pass (%.3f s; %s)\n", S.host_filter_s, S.host_filter_reason ? S.host_filter_reason : "--dry-run");
       }
     }
+  }
+  if (S.report_device && !S.device_filter) {
+    S.device_filter = true;  // (as for --mind below: every listed row is loaded under the all-pairs plan, run_prune() writes the reports and plans afterwards)
+    S.kept_sample_ct = founder_ct;
   }
   if (S.mind_device && !S.device_filter) {
     // (no count filter, or none that reached the block above: the rows --mind counts over are loaded under the all-pairs plan all the same, chromosome 0

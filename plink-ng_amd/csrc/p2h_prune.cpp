@@ -132,6 +132,12 @@ struct PruneJob {
     P.window_is_bp = A.window_is_bp;
     P.plink1_order = (A.order == 1);
     P.prune_last_param = A.r2;
+    if (!A.have_prune) {  // a run of reports alone: rows, count pass and records under the all-pairs plan, no window is ever used
+      P.prune_window_size = 2;
+      P.prune_window_incr = 1;
+      P.window_is_bp = 0;
+      P.prune_last_param = 0.5;
+    }
   }
 
   // --dry-run: the plan only (no device)
@@ -808,6 +814,79 @@ struct PruneJob {
     return true;
   }
 
+  // --missing / --freq / --geno-counts from the same load (Session::report_device): the records of the count pass hold every listed row's
+  // non-missing count and three genotype counts, the image its per-sample missing calls (ldp_sample_missing_counts), and a row with several
+  // ALT alleles the allele counts its major allele was chosen from (ldp_get_allele_counts; a row the host builds has none: the reader's
+  // allele pairs are counted instead).  Every kept sample is a founder here, so one set of counts serves all three reports.  Before
+  // ldp_restrict_variants(): the reports list what the table filters leave, chromosome 0 included.
+  void reports_on_device() {
+    const double t0 = now_s();
+    if ((m_ct != S.report_variants.size()) || (m_ct != variant_ct)) {
+      die(16, "\nError: internal: the reports list %zu variants and %u rows are loaded.\n", S.report_variants.size(), m_ct);
+    }
+    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
+    if (ldp_get_variant_recs(eng[0], 0, m_ct, recs.data())) {
+      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+    }
+    ReportCounts C;
+    C.kept_sample_ct = founder_ct;
+    C.variants.resize(m_ct);
+    C.missing.resize(m_ct);
+    C.f_ref2.resize(m_ct);
+    C.f_het.resize(m_ct);
+    C.f_alt2.resize(m_ct);
+    std::vector<uint32_t> offsets(static_cast<size_t>(m_ct) + 1, 0);
+    for (uint32_t q = 0; q < m_ct; ++q) {
+      const uint32_t raw_v = inc[mk[q]];
+      if (raw_v != S.report_variants[q]) {
+        die(16, "\nError: internal: row %u holds variant %u, the reports list %u there.\n", q, raw_v, S.report_variants[q]);
+      }
+      C.variants[q] = raw_v;
+      C.missing[q] = founder_ct - recs[q].nm_ct;
+      C.f_ref2[q] = recs[q].n_homref;
+      C.f_het[q] = recs[q].n_het;
+      C.f_alt2[q] = recs[q].n_homalt;
+      offsets[q + 1] = offsets[q] + ((A.rep_freq && (V.alt_ct[raw_v] > 1)) ? (static_cast<uint32_t>(V.alt_ct[raw_v]) + 1) : 0u);
+    }
+    size_t multi_device = 0, multi_host = 0;
+    if (offsets[m_ct]) {
+      std::vector<uint32_t> counts(offsets[m_ct]);
+      std::vector<uint8_t> has(m_ct), lo, hi;
+      if (ldp_get_allele_counts(eng[0], 0, m_ct, offsets.data(), counts.data(), has.data())) {
+        die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+      }
+      for (uint32_t q = 0; q < m_ct; ++q) {
+        if (offsets[q + 1] == offsets[q]) {
+          continue;
+        }
+        std::vector<uint32_t>& dst = C.allele_cts[q];
+        if (has[q]) {
+          dst.assign(counts.begin() + offsets[q], counts.begin() + offsets[q + 1]);
+          ++multi_device;
+        } else {
+          reports_count_alleles_host(S, C.variants[q], &lo, &hi, &dst);
+          ++multi_host;
+        }
+      }
+    }
+    C.sample_missing.assign(raw_sample_ct, 0);
+    if (A.rep_smiss()) {
+      std::vector<uint32_t> by_column(std::max<uint32_t>(founder_ct, 1), 0);
+      if (ldp_sample_missing_counts(eng[0], 0, m_ct, by_column.data())) {
+        die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+      }
+      for (uint32_t f = 0; f < founder_ct; ++f) {
+        C.sample_missing[founder_idx[f]] = by_column[f];  // (column f of the image is founder f of the file: every kept sample is a founder here)
+      }
+    }
+    const double t1 = now_s();
+    write_reports(S, C);
+    if (A.timing) {
+      logprintf("[timing] reports: from the device's count pass (%u rows; records%s %.3f s, writing %.3f s; allele counts of %zu multiallelic rows from the device, %zu from the reader)\n",
+                m_ct, A.rep_smiss() ? " and the per-sample read of the image" : "", t1 - t0, now_s() - t1, multi_device, multi_host);
+    }
+  }
+
   // --geno / --maf / --max-maf / --mac / --max-mac from the records the load's own count pass left on the device (nm_ct and the three
   // genotype counts of every row, over the founders = the kept samples: device_filter_refusal): the arithmetic of the host's pass
   // (CountFilters), then the engine drops the variants that go and plans over the rest (ldp_restrict_variants), and the session's variant
@@ -1226,6 +1305,9 @@ struct PruneJob {
   }
 
   int run() {
+    if ((!A.have_prune) && !S.report_device) {
+      finish();  // a run of reports alone whose reports the host's pass wrote (load_inputs): no device is touched
+    }
     set_params();
     if (A.dry_run) {
       return dry_run();
@@ -1250,6 +1332,13 @@ struct PruneJob {
       t_rows1 = now_s();
       if (S.mind_device && mind_on_device()) {
         return 0;  // (S.restart: main() starts over without the removed samples)
+      }
+      if (S.report_device) {
+        reports_on_device();
+        if (!A.have_prune) {
+          S.file_to_hbm_done();
+          finish();  // a run of reports alone stops here: no plan, no pair kernel
+        }
       }
       filter_on_device();
       check_unique_ids();

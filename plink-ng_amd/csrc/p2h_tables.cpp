@@ -210,12 +210,13 @@ void load_variants(const Args& A, Variants* V) {
   const std::string buf = zst ? slurp_zst(path) : slurp(path);
   bool header = false;
   int c_chrom = 0, c_pos = 3, c_id = 1, c_alt = -1, c_ref = -1, c_cm = -1, c_info = -1;
-  const bool keep_pr = (A.have_r2 && (A.r2_cols & kVcorColRef)) || (A.have_clump && (A.clump_cols & kClumpColRef));
+  const bool report_alleles = A.rep_freq || A.rep_gcount;  // (.afreq / .acount / .gcount print REF, ALT and, where some REF is provisional, that)
+  const bool keep_pr = (A.have_r2 && (A.r2_cols & kVcorColRef)) || (A.have_clump && (A.clump_cols & kClumpColRef)) || report_alleles;
   const bool keep_cm = A.have_r2 && (A.ld_cm_radius != -1.0);
   double last_cm = -1.7976931348623157e308;
   std::string last_cm_chrom;
   const bool keep_alleles = (A.have_r2 && (A.r2_cols & (kVcorColRef | kVcorColAlt1 | kVcorColAlt | kVcorColMaj | kVcorColNonmaj))) ||
-                            A.have_clump;  // (--clump: an A1 column names alleles of multiallelic variants, and of all variants under --clump-force-a1)
+                            report_alleles || A.have_clump;  // (--clump: an A1 column names alleles of multiallelic variants, and of all variants under --clump-force-a1)
   constexpr int kCap = 64;
   Tok t[kCap];
   const char* p = buf.data();

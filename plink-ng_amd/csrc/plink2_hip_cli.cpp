@@ -17,7 +17,9 @@
 // inter-chr .vcor table with cols=, --ld-window, --ld-window-kb, --ld-window-cm, --ld-window-r2, --ld-snp / --ld-snps / --ld-snp-list,
 // --parallel; number formatting restated from dtoa_g.  --mind for every command: per-sample missing-call counts from the resident image where the job
 // allows it (ldp_sample_missing_counts; samples that go make the run start over without them, in this process), from a host pass otherwise.  --clump (several reports, --clump-allow-overlap, cols=, bins, -log10,
-// ranges, sex chromosomes, (variant, A1 allele) pairs of multiallelic sites).
+// ranges, sex chromosomes, (variant, A1 allele) pairs of multiallelic sites).  The count reports -- --missing (.smiss / .vmiss), --freq (.afreq / .acount),
+// --geno-counts (.gcount), default columns, beside a command or alone -- from the counts the load makes anyway (the count pass's records, the per-sample read
+// of the image, ldp_get_allele_counts) where the job allows it, from a host pass otherwise (p2h_reports.cpp: the one writer).
 // Not yet supported (reported as such with exit 63, never silently mis-handled): dosage data outside --indep-pairwise on the autosomes,
 // more than 254 ALT alleles (multiallelic sites on chrX/Y/MT are taken by every command since round 5), major-allele-oriented
 // r^2 outputs on chrY/MT.
