@@ -366,6 +366,19 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
  * sharded engines (world > 1), and after LDP_GENO_PHASED loads or loads through a sample map that makes het calls missing (the
  * image's columns are not the samples' hardcalls there). */
 int ldp_sample_missing_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, uint32_t* out);
+/* Per-sample het-call counts, missing-call counts and weighted missing-call sums from the resident image, for a host's --het
+ * (HetReport, plink2_misc.cc).  Over the variants v of [first_variant, first_variant + n) with include[v - first_variant] != 0
+ * (include NULL: all of them), for every sample s < founder_ct: het_ct[s] = the rows where s is heterozygous, missing_ct[s] = the
+ * rows where s has no call, and, when weight is given, missing_weight[s] = the sum of weight[v - first_variant] over the rows
+ * where s has no call, modulo 2^64 (weight NULL: missing_weight is not computed and may be NULL; when it is given all the same it
+ * is zeroed).  het_ct and missing_ct are required.  All outputs: host memory, founder_ct entries.  Contract, states and refusals
+ * are those of ldp_sample_missing_counts(): current indices, before or after ldp_restrict_variants(); n == 0 gives zeros; one read
+ * of the rows on the engine's stream, synchronised before the call returns; nothing of the engine changes; LDP_ERR_STATE before
+ * every row of the range is loaded, LDP_ERR_INVALID for a range beyond variant_ct or a missing output, LDP_ERR_UNSUPPORTED on
+ * engines that keep bit-planes, on sharded engines, and after LDP_GENO_PHASED loads or loads through a sample map that makes het
+ * calls missing. */
+int ldp_sample_het_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, const uint64_t* weight, uint32_t* het_ct, uint32_t* missing_ct,
+                          uint64_t* missing_weight);
 /* major-allele frequencies (GetAlleleFreq(..., maj_alleles[v]), plink2_ld.cc:915) for LDP_GENO_INVERSE
  * input; for REF/BED input the engine derives them itself and this call overrides them. */
 int ldp_set_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, const double* maj_freqs);

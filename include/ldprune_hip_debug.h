@@ -112,6 +112,13 @@ int ldp_debug_get_compact_stats(const ldp_engine* e, uint64_t* rows_compacted, u
  * of the image they read (rows x row pitch).  Any pointer may be NULL. */
 int ldp_debug_get_sample_missing_stats(const ldp_engine* e, double* ms_kernel, uint64_t* bytes_read);
 
+/* ldp_sample_het_counts() with its test and measurement hooks as arguments -- the call keeps no state in the engine --: slab_rows cuts the
+ * rows into slabs of that many (at most 8160, as for "sample_missing_slab_rows"; 0 = chosen by the launch; results never depend on it);
+ * *ms_kernel and *bytes_read (either may be NULL) receive the device time of the kernel launches (HIP events on the engine's stream) and
+ * the bytes of the image they read (rows x row pitch). */
+int ldp_debug_sample_het_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, const uint64_t* weight, uint32_t* het_ct, uint32_t* missing_ct,
+                                uint64_t* missing_weight, uint32_t slab_rows, double* ms_kernel, uint64_t* bytes_read);
+
 /* What the last ldp_r2_phased_* call on this engine did (ldp_counters has no room left for it): the pairs its device-side filter saw
  * and the pairs it dropped (both 0 for the calls that do not filter), and the device time, HIP events on the engine's stream, of the
  * double-heterozygote product kernel (ldp_pair_phased.hip) and of the six-integer pair launches of the same call, summed over its

@@ -116,6 +116,7 @@ CABI_SYMBOLS = [
     "ldp_allgather_removed", "ldp_comm_init_all", "ldp_comm_destroy", "ldp_shard_segment_words", "ldp_pack_removed_segment", "ldp_stitch_removed_segments", "ldp_load_pgen_records", "ldp_load_pgen_records_phased", "ldp_pgen_file_bytes", "ldp_pgen_record_index", "ldp_device_numa_node",
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
+    "ldp_sample_het_counts", "ldp_debug_sample_het_counts",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
     "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass", "ldp_get_allele_counts",
 ]
@@ -123,7 +124,7 @@ CABI_SYMBOLS = [
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ("ldp_kernels.hip", "ldp_codes.hip", "ldp_pair_mfma.hip", "ldp_pair_wide.hip", "ldp_pred_csr.hip", "ldp_pgen_decode.hip", "ldp_synth.hip", "ldp_engine.cpp", "ldp_engine_run.cpp", "ldp_engine_r2.cpp",
-                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
+                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_sample_het.hip", "ldp_engine_sample_het.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
                                           "ldp_pair_phased.hip", "ldp_engine_phased.cpp", "ldp_phased_ld.cpp")]
 
 
@@ -176,7 +177,7 @@ def build_library(force=False, verbose=False, measure=False):
 def cli_sources():
     """the front-end's translation units: main() + one unit per concern (csrc/p2h_cli.h is what they share)"""
     return [os.path.join(CSRC, f) for f in ("plink2_hip_cli.cpp", "p2h_util.cpp", "p2h_args.cpp", "p2h_tables.cpp", "p2h_inputs.cpp", "p2h_clump.cpp", "p2h_r2.cpp",
-                                            "p2h_r2_phased.cpp", "p2h_prune.cpp", "p2h_reports.cpp")]
+                                            "p2h_r2_phased.cpp", "p2h_prune.cpp", "p2h_reports.cpp", "p2h_het.cpp")]
 
 
 def build_cli(force=False, verbose=False):
@@ -243,6 +244,8 @@ def lib():
     L.ldp_debug_get_compact_stats.argtypes = [vp, u64p, u64p, u64p, f64p]
     L.ldp_sample_missing_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p]
     L.ldp_debug_get_sample_missing_stats.argtypes = [vp, f64p, u64p]
+    L.ldp_sample_het_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), u64p, u32p, u32p, u64p]
+    L.ldp_debug_sample_het_counts.argtypes = L.ldp_sample_het_counts.argtypes + [ctypes.c_uint32, f64p, u64p]
     L.ldp_load_pgen_records.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
                                         ctypes.POINTER(ldp_pgen_rec), ctypes.c_uint32, u32p]
     L.ldp_load_pgen_records_phased.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
@@ -892,6 +895,39 @@ class LdPruneEngine:
         ms, nb = ctypes.c_double(), ctypes.c_uint64()
         self._ck(self._L.ldp_debug_get_sample_missing_stats(self._h, ctypes.byref(ms), ctypes.byref(nb)))
         return {"ms_kernel": float(ms.value), "bytes_read": int(nb.value)}
+
+    def sample_het_counts(self, first=0, n=None, include=None, weight=None, slab_rows=None, stats=None):
+        """ldp_sample_het_counts: per sample, over the variants of [first, first + n) whose `include` byte is non-zero (None: all), the rows
+        where it is heterozygous, the rows where it has no call, and (weight: uint64 per variant of the range) the sum modulo 2^64 of the
+        weights of the rows where it has no call.  Returns (het_ct, missing_ct, missing_weight), uint32 / uint32 / uint64 arrays of
+        founder_ct entries; missing_weight is None without weight.  slab_rows (rows per slab) or stats (a dict that receives 'ms_kernel' and
+        'bytes_read') take the call through ldp_debug_sample_het_counts, the same pass with its test hooks as arguments."""
+        n = self.variant_ct - first if n is None else n
+        fc = max(self.founder_ct, 1)
+        het, mis = np.zeros(fc, dtype=np.uint32), np.zeros(fc, dtype=np.uint32)
+        inc_p = w_p = mw_p = mw = None
+        if include is not None:
+            include = np.ascontiguousarray(include, dtype=np.uint8)
+            if include.size != n:
+                raise ValueError("include needs one byte per variant of the range")
+            inc_p = _ptr(include, ctypes.c_uint8) if n else None
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, dtype=np.uint64)
+            if weight.size != n:
+                raise ValueError("weight needs one entry per variant of the range")
+            mw = np.zeros(fc, dtype=np.uint64)
+            # (an empty range still asks for the weighted sums: a pointer the library will not read)
+            w_p = _ptr(weight if n else np.zeros(1, dtype=np.uint64), ctypes.c_uint64)
+            mw_p = _ptr(mw, ctypes.c_uint64)
+        if (slab_rows is None) and (stats is None):
+            self._ck(self._L.ldp_sample_het_counts(self._h, int(first), int(n), inc_p, w_p, _ptr(het, ctypes.c_uint32), _ptr(mis, ctypes.c_uint32), mw_p))
+        else:
+            ms, nb = ctypes.c_double(), ctypes.c_uint64()
+            self._ck(self._L.ldp_debug_sample_het_counts(self._h, int(first), int(n), inc_p, w_p, _ptr(het, ctypes.c_uint32), _ptr(mis, ctypes.c_uint32), mw_p,
+                                                         int(slab_rows or 0), ctypes.byref(ms), ctypes.byref(nb)))
+            if stats is not None:
+                stats.update(ms_kernel=float(ms.value), bytes_read=int(nb.value))
+        return het[:self.founder_ct], mis[:self.founder_ct], (None if mw is None else mw[:self.founder_ct])
 
     def release_device(self):
         """Free the engine's device memory, keep its plan (ldp_release_device)."""

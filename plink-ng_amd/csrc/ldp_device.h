@@ -416,6 +416,10 @@ hipError_t launch_gather_bytes(uint8_t* dst, const uint8_t* src, const uint32_t*
 // ldp_sample_missing.hip: counts[s] += missing calls of sample s < founder_ct over n_rows rows of the code image from row0 on (slab_rows_opt 0: slabs chosen by the launch)
 hipError_t launch_sample_missing(const uint8_t* codes, uint64_t pitch, uint64_t row0, uint32_t n_rows, uint32_t founder_ct, uint32_t* counts, uint32_t slab_rows_opt,
                                  hipStream_t stream);
+// ldp_sample_het.hip: het_ct[s] += het calls, missing_ct[s] += missing calls, missing_weight[s] += weights of the missing calls (weight != NULL) of sample s < founder_ct
+// over the included rows; include (NULL: all) / weight: device arrays of n_rows entries
+hipError_t launch_sample_het(const uint8_t* codes, uint64_t pitch, uint64_t row0, uint32_t n_rows, uint32_t founder_ct, const uint8_t* include, const uint64_t* weight,
+                             uint32_t* het_ct, uint32_t* missing_ct, uint64_t* missing_weight, uint32_t slab_rows_opt, hipStream_t stream);
 hipError_t launch_pair_stats_ref_codes(const uint8_t* codes, uint64_t code_row_bytes, const ldp_variant_rec* recs, const uint32_t* first, const uint32_t* second,
                                        uint32_t n_pairs, ldp_pair_stats_t* out, hipStream_t stream);
 constexpr double kSmallEpsilon = 0.00000000000005684341886080801486968994140625;  // 2^-44 (plink2_float.h:119)

@@ -811,6 +811,35 @@ bool parse_misc_flags(Args& A, ArgCursor& c, const std::string& f) {
 // modifier the reference knows is refused by name (exit 63); what the reference rejects is rejected with its message (exit 8)
 bool parse_report_flags(Args& A, ArgCursor& c, const std::string& f) {
   LDP_ARG_FAMILY_PROLOGUE;
+  if (f == "--het") {  // plink2.cc:7116-7145: ['zs'] ['small-sample'] ['cols='...], at most three
+    std::vector<std::string> mods;
+    while ((i + 1 < argc) && (argv[i + 1][0] != '-')) {
+      mods.push_back(argv[++i]);
+    }
+    if (mods.size() > 3) {
+      die(8, "Error: --het accepts at most 3 arguments.\n");
+    }
+    for (const std::string& m : mods) {
+      if (m == "zs") {
+        A.het_zs = true;
+      } else if (m == "small-sample") {
+        A.het_small_sample = true;
+      } else if (m.compare(0, 5, "cols=") == 0) {
+        die(63, "Error: the '%s' modifier of --het is not supported by plink2-hip (default columns, 'zs', 'small-sample' only).\n", m.c_str());
+      } else {
+        die(8, "Error: Invalid --het argument '%s'.\n", m.c_str());
+      }
+    }
+    A.het = true;
+    return true;
+  }
+  if (f == "--bad-freqs") {
+    A.bad_freqs = true;
+    return true;
+  }
+  if (f == "--read-freq") {
+    die(63, "Error: --read-freq is not supported by plink2-hip: --het takes its allele frequencies from the founders of the fileset.\n");
+  }
   if ((f != "--missing") && (f != "--freq") && (f != "--geno-counts") && (f != "--nonfounders")) {
     return false;
   }
@@ -887,7 +916,7 @@ void check_flag_combinations(Args& A) {
   } else if (A.clump_unphased) {
     die(8, "Error: --clump-unphased must be used with --clump.\n");
   }
-  if (!A.have_prune && !A.have_r2 && !A.any_report()) {
+  if (!A.have_prune && !A.have_r2 && !A.any_report() && !A.het) {
     die(8, "Error: no command given (plink2-hip implements --indep-pairwise and --r2-unphased matrices).\n");
   }
   if (A.have_prune && (A.parallel_tot != 1)) {

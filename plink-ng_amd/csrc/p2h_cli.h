@@ -217,6 +217,9 @@ struct Args {
   bool any_report() const { return rep_missing || rep_freq || rep_gcount; }
   bool rep_smiss() const { return rep_missing && !rep_variant_only; }
   bool rep_vmiss() const { return rep_missing && !rep_sample_only; }
+  // --het ['zs'] ['small-sample'] (p2h_het.cpp): after every filter, over the variants they leave -- a command of its own or beside any other
+  bool het = false, het_zs = false, het_small_sample = false;
+  bool bad_freqs = false;  // --bad-freqs: --het may estimate allele frequencies from fewer than 50 founders (plink2.cc:2076)
   bool timing = false;    // --timing: print per-phase wall times
   bool dry_run = false;  // parse + plan only, print the parameters exactly (%a) and exit: used by the CPU tests
 };
@@ -565,6 +568,10 @@ struct Session {
   // pass in load_inputs(), which says why; report_variants: what the reports list (== inc[] when run_prune() writes them)
   bool report_device = false;
   const char* report_host_reason = nullptr;
+  // --het: from the resident image after the filters (het_device; device_filter is set with it, as for mind_device), or from the host's pass over
+  // the rows of the final variant list, which says why
+  bool het_device = false;
+  const char* het_host_reason = nullptr;
   std::vector<uint32_t> report_variants;
   double t_begin_first = 0.0;            // restarted run: main()'s first start (the total of --timing covers both loads)
   // (... and, once the runtime is up, this thread -- the one that creates the engines, their copy threads and their pinned staging -- moves next to the device)
@@ -636,6 +643,43 @@ void reports_list_variants(Session& S, bool chr_filter, const std::unordered_set
 void reports_count_alleles_host(const Session& S, uint32_t raw_variant, std::vector<uint8_t>* lo, std::vector<uint8_t>* hi, std::vector<uint32_t>* counts);
 // the files and their log lines, in the reference's order
 void write_reports(const Session& S, const ReportCounts& C);
+
+// ---- --het (p2h_het.cpp): per-sample observed and expected heterozygosity, HetReport (plink2_misc.cc) with its default columns ----
+// One variant's expected heterozygosity from the founders' allele counts (cts[0] REF, cts[1 ..] the ALT alleles), as HetThread forms it:
+// from the frequencies (count * (1 / total); nothing observed: 1 / alleles each) or, small_sample, from the counts.  false: the reference
+// skips the variant and counts it in its "monomorphic" warning.
+bool het_expected(const uint32_t* cts, uint32_t allele_ct, bool small_sample, double* ehet);
+// het_all_missing_skipped: one more variant the reference skips and counts as monomorphic.  A variable-width .pgen stores a variant nobody has a
+// call at as an empty list of exceptions from "missing", and HetThread's branch for such records (plink2_misc.cc:9952-9956) skips it, while
+// the same variant in a .bed or a fixed-width .pgen counts with the frequency 1/2 of an unobserved allele and changes no sample's figures
+// (everybody misses it).  Both passes apply it where the file is variable-width (Session::direct_rows is NULL), the variant has one ALT allele
+// (the others are read in full, PgrGetM) and every kept sample misses the call.
+// What both sources of the per-sample sums go through -- the device's pass over the resident image (run_prune: ldp_sample_het_counts) and the
+// host's pass over the rows (het_host_pass) --, so that the two write the same bytes.  With m kept variants every ehet_v becomes the integer
+// q_v = llrint(ehet_v * 2^k), k = min(52, 62 - bit_length(m)); a sample's expected count is (sum of all q_v - sum of the q_v of the variants
+// it misses) * 2^-k: integer sums, the same in any order.
+struct HetPlan {
+  int k = 52;
+  uint64_t total = 0;              // sum of q_v over the kept variants
+  uint32_t kept = 0, skipped = 0;  // variants that count / that HetThread skips as monomorphic
+  std::vector<uint64_t> weight;    // per variant of the list: q_v, 0 for a skipped one
+  std::vector<uint8_t> include;    // per variant of the list: 1 = kept
+  // ehet: per variant of the list; ok: het_expected()'s answer for it
+  void build(const std::vector<double>& ehet, const std::vector<uint8_t>& ok);
+};
+// per sample of the file (kept samples only are read): het calls, missing calls and the summed q_v of the missing calls over the kept variants
+struct HetSums {
+  std::vector<uint32_t> het_ct, missing_ct;
+  std::vector<uint64_t> missing_weight;
+};
+// the reference's warning about skipped variants, <out>.het[.zst] and its log line
+void het_write(const Session& S, const HetPlan& plan, const HetSums& sums);
+// the log lines and errors HetReport has before it reads a genotype ('--het small-sample' without founders, non-autosomal variants excluded, none left);
+// non_autosomal: variants of the final list on chrX / chrY / MT, autosomal: the others
+void het_preamble(const Session& S, uint32_t autosomal, uint32_t non_autosomal);
+// the host's pass: the autosomal variants of the final list (S.inc), every kept sample; p2h_inputs.cpp, beside the other passes over the rows
+void het_host_pass(Session& S);
+void logprintf_ww(const char* fmt, ...);  // logprintf with the reference's word wrap at 79 columns (logprintfww)
 
 void load_inputs(Session& S, int argc, char** argv);
 int run_r2(Session& S);

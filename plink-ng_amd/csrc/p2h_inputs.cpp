@@ -275,7 +275,7 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
   if (g_dbg.host_filter) {
     return "--debug-host-filter";
   }
-  if (((!A.have_prune) && (A.have_r2 || !A.any_report())) || A.pairphase) {  // (a run of reports alone loads like the prune)
+  if (((!A.have_prune) && (A.have_r2 || !(A.any_report() || A.het))) || A.pairphase) {  // (a run of reports or of --het alone loads like the prune)
     return A.pairphase ? "--indep-pairphase plans its engines before the load" : "the r^2 outputs and --clump plan their engines before the load";
   }
   if (A.gpus != 1) {
@@ -587,6 +587,188 @@ static void reports_stage(Session& S, bool chr_filter, const std::unordered_set<
   }
 }
 
+// The --het stage of load_inputs(): what is refused, then where the sums come from -- the resident image after the filters (S.het_device: the
+// conditions of the count filters, device_filter_refusal, and rows that ARE the hardcalls of autosomal biallelic variants), or het_host_pass().
+static void het_stage(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
+  if (ldp_pgen_has_dosage(S.pg)) {
+    // (the reference takes the allele frequencies from the dosages where a record has them, plink2_data.cc:2421-2443)
+    die(63, "Error: %s holds dosage data, which --het of plink2-hip does not read.  Use plink2 --make-pgen erase-dosage first.\n", S.gpath.c_str());
+  }
+  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chromosome 0, 3 = chrX / chrY / MT
+  bool any_non_autosomal = false, any_multiallelic = false;
+  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
+    auto it = chr_state.find(V.chrom[v]);
+    if (it == chr_state.end()) {
+      const std::string& cur = V.chrom[v];
+      const int code = chrom_code(cur);
+      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
+                                       (A.autosome && !((code >= 1) && (code <= 22))));
+      bool zero = false;
+      const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
+      it = chr_state.emplace(cur, static_cast<uint8_t>(out ? 1 : (zero ? 2 : ((cls >= 3) ? 3 : 0)))).first;
+    }
+    if ((it->second == 1) || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
+      continue;
+    }
+    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
+      continue;
+    }
+    if ((it->second == 2) && (A.have_prune || (A.r2_table && !A.r2_inter))) {
+      // (the reference's --het counts unplaced variants as autosomal; the prune and the windowed tables strip them from the one list kept here)
+      die(63, "Error: --het beside %s with chromosome 0 variants ('%s') is not supported by plink2-hip: run --het on its own, or filter them out (--not-chr 0).\n",
+          A.have_prune ? "the prune" : "a windowed r^2 command", V.id[v].c_str());
+    }
+    any_non_autosomal = any_non_autosomal || (it->second == 3);
+    any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
+  }
+  uint32_t kept_samples = 0, founders = 0;
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    kept_samples += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
+    founders += S.is_founder[sx];
+  }
+  const char* reason = device_filter_refusal(A, false, kept_samples, founders);
+  if (!reason) {
+    reason = A.dry_run ? "--dry-run"
+             : ((founders < 2) ? "fewer than two founders (no engine)"
+             : ((founders > ldp_matrix_pipe_max_founders()) ? "more founders than the resident 2-bit image takes (the per-sample sums are read off it)"
+             : (any_non_autosomal ? "chrX / chrY / MT variants (their rows are built for engines of their own)"
+             : (any_multiallelic ? "multiallelic variants (their rows are collapsed on the way into the image)" : nullptr))));
+  }
+  if (A.dry_run) {
+    logprintf("dry-run: --het: %s%s\n", reason ? "host pass: " : "from the resident image", reason ? reason : "");
+  }
+  S.het_device = !reason;
+  S.het_host_reason = reason;
+}
+
+void het_host_pass(Session& S) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  const double t0 = now_s();
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  std::vector<uint32_t> todo;  // the autosomal variants of the final list (chromosome 0 counts as one, CountNonAutosomalVariants plink2_common.cc:3334)
+  uint32_t non_autosomal = 0;
+  for (size_t k = 0; k < S.inc.size(); ++k) {
+    if (S.vcls[k] >= 3) {
+      ++non_autosomal;
+    } else {
+      todo.push_back(S.inc[k]);
+    }
+  }
+  het_preamble(S, static_cast<uint32_t>(todo.size()), non_autosomal);
+  const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
+  std::vector<uint64_t> m_f(words, 0), m_s(words, 0);
+  uint32_t kept_samples = 0;
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    if (S.sample_kept.empty() || S.sample_kept[sx]) {
+      m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
+      ++kept_samples;
+    }
+    if (S.is_founder[sx]) {
+      m_f[sx >> 5] |= 1ull << (2 * (sx & 31));
+    }
+  }
+  const bool bed = (S.storage_mode == 0x01);
+  const uint64_t rec_bytes = S.rec_bytes;
+  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  // first pass: the founders' allele counts, hence every variant's expected heterozygosity and the plan of the integer sums
+  std::vector<RowCounts> fc(todo.size());
+  for_each_row_run(S.pg, S.gpath, S.direct_rows, rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
+    count_rows(rows, rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &fc[q]);
+  });
+  std::vector<double> ehet(todo.size(), 0.0);
+  std::vector<uint8_t> ok(todo.size(), 0);
+  std::vector<uint8_t> lo, hi;
+  std::vector<uint32_t> cts;
+  for (size_t q = 0; q < todo.size(); ++q) {
+    if (V.alt_ct[todo[q]] > 1) {
+      reports_count_alleles_host(S, todo[q], &lo, &hi, &cts);
+    } else {
+      cts.assign({2 * fc[q].ref2 + fc[q].het, 2 * fc[q].alt2 + fc[q].het});
+    }
+    ok[q] = het_expected(cts.data(), static_cast<uint32_t>(cts.size()), A.het_small_sample, &ehet[q]) ? 1 : 0;
+    if (ok[q] && (!S.direct_rows) && (V.alt_ct[todo[q]] <= 1) && (fc[q].missing == kept_samples)) {
+      ok[q] = 0;  // (het_all_missing_skipped, p2h_cli.h)
+    }
+  }
+  HetPlan plan;
+  plan.build(ehet, ok);
+  // second pass: per kept sample the het calls, the missing calls and the q_v of the missing calls, over the kept variants
+  const uint64_t kLo = 0x5555555555555555ull;
+  const uint64_t row_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
+  std::vector<HetSums> part(nthreads);
+  for (HetSums& p : part) {
+    p.het_ct.assign(32 * words, 0);
+    p.missing_ct.assign(32 * words, 0);
+    p.missing_weight.assign(32 * words, 0);
+  }
+  for_each_row_run(S.pg, S.gpath, S.direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t q) {
+    HetSums& p = part[t];
+    for (uint32_t r = 0; r < n; ++r) {
+      if ((!plan.include[q + r]) || (V.alt_ct[todo[q + r]] > 1)) {
+        continue;
+      }
+      const uint8_t* row = rows + static_cast<uint64_t>(r) * rec_bytes;
+      const uint64_t wt = plan.weight[q + r];
+      for (size_t w = 0; w < words; ++w) {
+        uint64_t x = 0;
+        const uint64_t left = row_bytes - 8 * w;
+        memcpy(&x, row + 8 * w, (left < 8) ? left : 8);
+        const uint64_t b_lo = x & kLo, b_hi = (x >> 1) & kLo;
+        // .pgen: 01 het, 11 missing; .bed: 10 het, 01 missing (pgenlib_read.cc:2157)
+        uint64_t het = (bed ? (b_hi & ~b_lo) : (b_lo & ~b_hi)) & m_s[w];
+        uint64_t miss = (bed ? (b_lo & ~b_hi) : (b_lo & b_hi)) & m_s[w];
+        while (het) {
+          ++p.het_ct[32 * w + (static_cast<uint32_t>(__builtin_ctzll(het)) >> 1)];
+          het &= het - 1;
+        }
+        while (miss) {
+          const uint32_t sx = static_cast<uint32_t>(32 * w) + (static_cast<uint32_t>(__builtin_ctzll(miss)) >> 1);
+          ++p.missing_ct[sx];
+          p.missing_weight[sx] += wt;
+          miss &= miss - 1;
+        }
+      }
+    }
+  });
+  HetSums sums;
+  sums.het_ct.assign(raw_sample_ct, 0);
+  sums.missing_ct.assign(raw_sample_ct, 0);
+  sums.missing_weight.assign(raw_sample_ct, 0);
+  for (const HetSums& p : part) {
+    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+      sums.het_ct[sx] += p.het_ct[sx];
+      sums.missing_ct[sx] += p.missing_ct[sx];
+      sums.missing_weight[sx] += p.missing_weight[sx];
+    }
+  }
+  // a variant with several ALT alleles: every call with two different alleles is a het one (HetThread :10063-10079), from the reader's allele pairs
+  for (size_t q = 0; q < todo.size(); ++q) {
+    if (plan.include[q] && (V.alt_ct[todo[q]] > 1)) {
+      reports_count_alleles_host(S, todo[q], &lo, &hi, &cts);
+      for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+        if ((!S.sample_kept.empty()) && !S.sample_kept[sx]) {
+          continue;
+        }
+        if (lo[sx] == 255) {
+          ++sums.missing_ct[sx];
+          sums.missing_weight[sx] += plan.weight[q];
+        } else if (lo[sx] != hi[sx]) {
+          ++sums.het_ct[sx];
+        }
+      }
+    }
+  }
+  het_write(S, plan, sums);
+  if (A.timing) {
+    logprintf("[timing] --het: host pass (%.3f s; %s)\n", now_s() - t0, S.het_host_reason ? S.het_host_reason : "the r^2 outputs and --clump plan their engines before the load");
+  }
+}
+
 void load_inputs(Session& S, int argc, char** argv) {
   S.t_begin = S.t_begin_first ? S.t_begin_first : now_s();
   S.A = parse_args(argc, argv);
@@ -618,7 +800,7 @@ void load_inputs(Session& S, int argc, char** argv) {
   const bool sample_filter = (!A.keep_files.empty()) || (!A.remove_files.empty());
   const bool mind_on = (A.mind < 1.0);  // plink2.cc:8910
   std::vector<std::pair<std::string, std::string>> parent_keys;
-  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on || A.rep_smiss()) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
+  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on || A.rep_smiss() || A.het) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
                &S.sample_sids);
   // --make-founders (MakeFounders, plink2_filter.cc:4372-4443): a non-founder with a parent (both, with 'require-2-missing') that
   // is not among the samples in play becomes a founder; 'first' applies it before --keep / --remove, else after them
@@ -751,6 +933,19 @@ void load_inputs(Session& S, int argc, char** argv) {
     }
     die(13, "Error: This run estimates linkage disequilibrium between variants, but there\nare less than 50 founders to estimate from.  --make-founders may help.\n(Strictly speaking, you can also override this error with --bad-ld, but this is\nalmost always a bad idea.)\n");
   }
+  if (A.het && (!A.het_small_sample) && !A.bad_freqs) {  // plink2.cc:2073-2088: --het needs decent allele frequencies (no --read-freq, no --nonfounders here)
+    uint32_t sample_ct = 0;
+    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+      sample_ct += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
+    }
+    if ((sample_ct >= 50) && (founder_ct < 50)) {
+      die(13, "Error: This run requires decent allele frequencies, but they aren't being\nloaded with --read-freq, and less than 50 founders are available to impute them\nfrom.  Possible solutions:\n* You can use --nonfounders to include nonfounders when imputing allele\n  frequencies.\n* You can generate (with --freq) or obtain an allele frequency file based on a\n  larger similar-population reference dataset, and load it with --read-freq.\n* (Not recommended) You can override this error with --bad-freqs.\n");
+    }
+    if (sample_ct < 50) {
+      die(13, "Error: This run requires decent allele frequencies, but they aren't being\nloaded with --read-freq, and less than 50 samples are available to impute them\nfrom.\nYou should generate (with --freq) or obtain an allele frequency file based on a\nlarger similar-population reference dataset, and load it with --read-freq.\n%s",
+          (sample_ct != founder_ct) ? "If you're certain you want to proceed without doing that, use --bad-freqs to\noverride this error, and consider using --nonfounders as well.\n" : "");
+    }
+  }
   if ((founder_ct < 2) && (A.have_prune || A.have_r2)) {
     die(7, "Error: %s requires at least two founders. (--make-founders may come in handy here.)\n", A.have_prune ? (A.pairphase ? "--indep-pairphase" : "--indep-pairwise") : "--r2-unphased");
   }
@@ -804,7 +999,10 @@ void load_inputs(Session& S, int argc, char** argv) {
     reports_stage(S, chr_filter, extract_ids, exclude_ids);
   }
   // (a run of reports alone: nothing reads the filtered variant list, and the reference applies no variant filter then)
-  if ((freq_filter || (A.geno != 1.0)) && (A.have_prune || A.have_r2)) {
+  if (A.het) {
+    het_stage(S, chr_filter, extract_ids, exclude_ids);
+  }
+  if ((freq_filter || (A.geno != 1.0)) && (A.have_prune || A.have_r2 || A.het)) {
     std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome
     std::vector<uint32_t> todo;
     for (uint32_t v = 0; v < raw_variant_ct; ++v) {
@@ -895,6 +1093,10 @@ void load_inputs(Session& S, int argc, char** argv) {
   if (S.mind_device && !S.device_filter) {
     // (no count filter, or none that reached the block above: the rows --mind counts over are loaded under the all-pairs plan all the same, chromosome 0
     // included, and run_prune() plans over what is left once the samples are decided)
+    S.device_filter = true;
+    S.kept_sample_ct = founder_ct;
+  }
+  if (S.het_device && !S.device_filter) {  // (the same again: --het reads the image after the filters, whoever decided them)
     S.device_filter = true;
     S.kept_sample_ct = founder_ct;
   }
@@ -1034,6 +1236,11 @@ void load_inputs(Session& S, int argc, char** argv) {
     m_bps[q] = bps[mk[q]];
   }
   g_log_mute = false;
+  if (A.het && A.have_r2) {
+    // (the r^2 outputs and --clump keep the host's filters: the variant list is final here.  Beside the prune, or alone, run_prune() calls the
+    // pass once its list is -- after the device's filters, after a --mind decided there)
+    het_host_pass(S);
+  }
 }
 
 

@@ -887,6 +887,66 @@ struct PruneJob {
     }
   }
 
+  // --het from the resident image (Session::het_device), after the filters and on the restricted engine: the records of the count pass give
+  // every row's genotype counts, hence its expected heterozygosity (het_expected) and the integer weight it enters the sums with (HetPlan);
+  // one ldp_sample_het_counts() call reads the image in the sample direction -- het calls, missing calls and the summed weights of the missing
+  // calls per column --, and the writer the host's pass uses does the rest.  One engine, autosomes only, no multiallelic variant, every kept
+  // sample a founder: row q is variant q of the list, column f founder f of the file.
+  void het_on_device() {
+    const double t0 = now_s();
+    if (m_ct != variant_ct) {
+      die(16, "\nError: internal: --het lists %u variants and %u rows are loaded.\n", variant_ct, m_ct);
+    }
+    het_preamble(S, m_ct, 0);
+    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
+    if (ldp_get_variant_recs(eng[0], 0, m_ct, recs.data())) {
+      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+    }
+    std::vector<double> ehet(m_ct, 0.0);
+    std::vector<uint8_t> ok(m_ct, 0);
+    for (uint32_t q = 0; q < m_ct; ++q) {
+      const uint32_t cts[2] = {2 * recs[q].n_homref + recs[q].n_het, 2 * recs[q].n_homalt + recs[q].n_het};
+      ok[q] = het_expected(cts, 2, A.het_small_sample, &ehet[q]) ? 1 : 0;
+      if (ok[q] && (!direct_rows) && !recs[q].nm_ct) {
+        ok[q] = 0;  // (het_all_missing_skipped, p2h_cli.h: the kept samples are the founders here)
+      }
+    }
+    HetPlan plan;
+    plan.build(ehet, ok);
+    const uint32_t cols = std::max<uint32_t>(founder_ct, 1);
+    std::vector<uint32_t> het_col(cols, 0), mis_col(cols, 0);
+    std::vector<uint64_t> mw_col(cols, 0);
+    double ms = 0.0;
+    uint64_t bytes = 0;
+    // (--timing: the same pass through its measurement hook, which also returns the kernel's time and the bytes it read)
+    if (A.timing ? ldp_debug_sample_het_counts(eng[0], 0, m_ct, plan.include.data(), plan.weight.data(), het_col.data(), mis_col.data(), mw_col.data(), 0, &ms, &bytes)
+                 : ldp_sample_het_counts(eng[0], 0, m_ct, plan.include.data(), plan.weight.data(), het_col.data(), mis_col.data(), mw_col.data())) {
+      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+    }
+    HetSums sums;
+    sums.het_ct.assign(raw_sample_ct, 0);
+    sums.missing_ct.assign(raw_sample_ct, 0);
+    sums.missing_weight.assign(raw_sample_ct, 0);
+    for (uint32_t f = 0; f < founder_ct; ++f) {
+      sums.het_ct[founder_idx[f]] = het_col[f];
+      sums.missing_ct[founder_idx[f]] = mis_col[f];
+      sums.missing_weight[founder_idx[f]] = mw_col[f];
+    }
+    const double t1 = now_s();
+    het_write(S, plan, sums);
+    if (A.timing) {
+      logprintf("[timing] --het: from the resident image (%u rows, %u of them kept; kernel %.3f ms = %.0f GB/s; records, plan and the call %.3f s, writing %.3f s)\n", m_ct, plan.kept, ms,
+                (ms > 0.0) ? (static_cast<double>(bytes) / 1e9 / (ms * 1e-3)) : 0.0, t1 - t0, now_s() - t1);
+    }
+  }
+  void het_stage() {
+    if (S.het_device) {
+      het_on_device();
+    } else {
+      het_host_pass(S);
+    }
+  }
+
   // --geno / --maf / --max-maf / --mac / --max-mac from the records the load's own count pass left on the device (nm_ct and the three
   // genotype counts of every row, over the founders = the kept samples: device_filter_refusal): the arithmetic of the host's pass
   // (CountFilters), then the engine drops the variants that go and plans over the rest (ldp_restrict_variants), and the session's variant
@@ -1305,8 +1365,11 @@ struct PruneJob {
   }
 
   int run() {
-    if ((!A.have_prune) && !S.report_device) {
-      finish();  // a run of reports alone whose reports the host's pass wrote (load_inputs): no device is touched
+    if ((!A.have_prune) && (!S.report_device) && !(A.het && S.device_filter)) {
+      if (A.het) {
+        het_host_pass(S);  // (the host's filters made the list final in load_inputs)
+      }
+      finish();  // a run of reports or of --het alone that the host's passes served: no device is touched
     }
     set_params();
     if (A.dry_run) {
@@ -1335,12 +1398,20 @@ struct PruneJob {
       }
       if (S.report_device) {
         reports_on_device();
-        if (!A.have_prune) {
+        if ((!A.have_prune) && !A.het) {
           S.file_to_hbm_done();
           finish();  // a run of reports alone stops here: no plan, no pair kernel
         }
       }
-      filter_on_device();
+      if (A.have_prune || S.count_filters) {
+        filter_on_device();
+      }
+      if (!A.have_prune) {
+        report_filter_timing();
+        het_stage();  // --het alone, after the filters: no band plan, no pair kernel
+        S.file_to_hbm_done();
+        finish();
+      }
       check_unique_ids();
     }
     if (subcontig_ct || !xk.empty() || !yk.empty() || !tk.empty()) {
@@ -1380,6 +1451,9 @@ struct PruneJob {
       run_sex_chromosomes();
     }
     write_lists();
+    if (A.het) {
+      het_stage();  // (right behind LdPrune, plink2.cc:2958; the restricted engine's image is as the filters left it)
+    }
     finish();
   }
 };

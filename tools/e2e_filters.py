@@ -44,7 +44,7 @@ def run(binary, cwd, pfile, filters, kb, r2, out, extra=(), runs=2, timeout_s=15
         walls.append(wall)
     lines = txt.splitlines()
     return {"rc": rc, "wall_s": min(walls) if walls else None, "wall_s_runs": walls,
-            "variant_filters_line": [ln for ln in lines if ("variant filters:" in ln) or ("[timing] compaction:" in ln) or ("sample filter (--mind):" in ln)],
+            "variant_filters_line": [ln for ln in lines if ("variant filters:" in ln) or ("[timing] compaction:" in ln) or ("sample filter (--mind):" in ln) or ("[timing] --het:" in ln)],
             "filter_log_lines": [ln.strip() for ln in lines if "removed due to" in ln],
             "removed_line": [ln.strip() for ln in lines if re.search(r"\d+/\d+ variants removed", ln)][-1:],
             "timing_lines": [ln for ln in lines if ln.startswith("[timing]")][:12], "tail": txt[-400:] if rc else ""}
@@ -115,6 +115,11 @@ def main():
             leg["device_records"] = run(support.CLI_BIN, tmp, pfile, filters, kb, cfg["r2"], pfile + "_dev", extra=["--timing"], runs=args.runs)
             leg["host_pass"] = run(support.CLI_BIN, tmp, pfile, filters, kb, cfg["r2"], pfile + "_host", extra=["--timing", "--debug-host-filter"], runs=args.runs)
             leg["host_pass"]["lists_identical_to_device_records"] = same_lists(tmp, pfile + "_dev", pfile + "_host")
+            if "--het" in filters:
+                try:
+                    leg["host_pass"]["het_identical_to_device_records"] = open(os.path.join(tmp, pfile + "_dev.het"), "rb").read() == open(os.path.join(tmp, pfile + "_host.het"), "rb").read()
+                except OSError:
+                    leg["host_pass"]["het_identical_to_device_records"] = False
             if args.other_bin:
                 leg["other_build"] = run(os.path.abspath(args.other_bin), tmp, pfile, filters, kb, cfg["r2"], pfile + "_other", extra=["--timing"], runs=args.runs)
                 leg["other_build"]["lists_identical_to_device_records"] = same_lists(tmp, pfile + "_dev", pfile + "_other")
