@@ -379,6 +379,30 @@ int ldp_sample_missing_counts(ldp_engine* e, uint32_t first_variant, uint32_t n,
  * calls missing. */
 int ldp_sample_het_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, const uint64_t* weight, uint32_t* het_ct, uint32_t* missing_ct,
                           uint64_t* missing_weight);
+/* The exact Hardy-Weinberg test of loaded rows, for a host's --hwe / --hardy, from the genotype counts the load's count pass left in the
+ * records on the device (n_homref, n_het, n_homalt of ldp_get_variant_recs(); diploid, one ALT allele).  For every variant v of
+ * [first_variant, first_variant + n): ln_p[v - first_variant] = the natural logarithm of the test's p-value -- conditional on the
+ * sample count N = hom1 + het + hom2 and the rarer allele's count, the probability of every het count no likelier than the observed
+ * one; with midp != 0 half of the probability of the het counts exactly as likely as the observed one, itself included, is taken off
+ * --, N = 0 giving p = 1 (0.5 with midp).  |ln_p - exact| <= (4 N + 64) 2^-52 + 4 |ln_p| 2^-52; p far below DBL_MIN is no special
+ * case.  flags (may be NULL), one byte per variant: bit 0 = a het count other than the observed one's two neighbours came within
+ * 4 * steps * 2^-52 of the observed likelihood and was counted as exactly as likely (the neighbours are compared in integers,
+ * exactly).  Both outputs: host memory, n entries.  Contract, states and refusals are those of ldp_sample_het_counts(): current
+ * indices, before or after ldp_restrict_variants(); n == 0 writes nothing; one kernel per run of owned rows on the engine's stream,
+ * synchronised before the call returns; nothing of the engine changes; LDP_ERR_STATE before every row of the range is loaded,
+ * LDP_ERR_INVALID for a range beyond variant_ct or a NULL ln_p, LDP_ERR_UNSUPPORTED on sharded engines and where a row's record
+ * carries no raw genotype counts: rows loaded as LDP_GENO_INVERSE, and engines that loaded LDP_GENO_PHASED rows or rows through a
+ * sample map that makes het calls missing.  The image is not read, so engines that keep bit-planes are served as well. */
+int ldp_hwe_ln_pvals(ldp_engine* e, uint32_t first_variant, uint32_t n, int midp, double* ln_p, uint8_t* flags /* may be NULL */);
+/* The same kernel on counts from anywhere: hom1, het, hom2, ln_p, flags (may be NULL) are host arrays of n entries, device a HIP
+ * device ordinal (-1: the current device).  The call copies the counts up, runs one launch on a stream of its own and returns when
+ * the results are back.  LDP_ERR_INVALID when a triple sums to 2^31 or more (nothing is computed), LDP_ERR_GPU without a device. */
+int ldp_hwe_ln_pvals_counts(int device, uint32_t n, const uint32_t* hom1, const uint32_t* het, const uint32_t* hom2, int midp, double* ln_p, uint8_t* flags);
+/* The same arithmetic for one triple on the calling thread, no device involved: what a host uses on counts from its own pass over
+ * the rows, and what device results at large N are compared against.  The device's log() and the host's may differ in the last
+ * bit; everything before it is the same sequence of IEEE operations.  flags (may be NULL) as above; a triple summing to 2^31 or
+ * more returns NaN with flag bit 7. */
+double ldp_hwe_ln_p_host(uint32_t hom1, uint32_t het, uint32_t hom2, int midp, uint8_t* flags);
 /* major-allele frequencies (GetAlleleFreq(..., maj_alleles[v]), plink2_ld.cc:915) for LDP_GENO_INVERSE
  * input; for REF/BED input the engine derives them itself and this call overrides them. */
 int ldp_set_maj_freqs(ldp_engine* e, uint32_t first_variant, uint32_t n, const double* maj_freqs);

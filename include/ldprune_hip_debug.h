@@ -119,6 +119,12 @@ int ldp_debug_get_sample_missing_stats(const ldp_engine* e, double* ms_kernel, u
 int ldp_debug_sample_het_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, const uint64_t* weight, uint32_t* het_ct, uint32_t* missing_ct,
                                 uint64_t* missing_weight, uint32_t slab_rows, double* ms_kernel, uint64_t* bytes_read);
 
+/* ldp_hwe_ln_pvals() / ldp_hwe_ln_pvals_counts() with their measurement hook as an argument -- neither keeps state --: *ms_kernel (may be
+ * NULL) receives the device time of the hwe_kernel launches (HIP events on the stream they run on). */
+int ldp_debug_hwe_ln_pvals(ldp_engine* e, uint32_t first_variant, uint32_t n, int midp, double* ln_p, uint8_t* flags, double* ms_kernel);
+int ldp_debug_hwe_ln_pvals_counts(int device, uint32_t n, const uint32_t* hom1, const uint32_t* het, const uint32_t* hom2, int midp, double* ln_p, uint8_t* flags,
+                                  double* ms_kernel);
+
 /* What the last ldp_r2_phased_* call on this engine did (ldp_counters has no room left for it): the pairs its device-side filter saw
  * and the pairs it dropped (both 0 for the calls that do not filter), and the device time, HIP events on the engine's stream, of the
  * double-heterozygote product kernel (ldp_pair_phased.hip) and of the six-integer pair launches of the same call, summed over its

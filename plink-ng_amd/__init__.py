@@ -117,6 +117,7 @@ CABI_SYMBOLS = [
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
     "ldp_sample_het_counts", "ldp_debug_sample_het_counts",
+    "ldp_hwe_ln_pvals", "ldp_hwe_ln_pvals_counts", "ldp_hwe_ln_p_host", "ldp_debug_hwe_ln_pvals", "ldp_debug_hwe_ln_pvals_counts",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
     "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass", "ldp_get_allele_counts",
 ]
@@ -124,7 +125,7 @@ CABI_SYMBOLS = [
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ("ldp_kernels.hip", "ldp_codes.hip", "ldp_pair_mfma.hip", "ldp_pair_wide.hip", "ldp_pred_csr.hip", "ldp_pgen_decode.hip", "ldp_synth.hip", "ldp_engine.cpp", "ldp_engine_run.cpp", "ldp_engine_r2.cpp",
-                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_sample_het.hip", "ldp_engine_sample_het.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
+                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_sample_het.hip", "ldp_engine_sample_het.cpp", "ldp_hwe.hip", "ldp_engine_hwe.cpp", "ldp_hwe_host.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
                                           "ldp_pair_phased.hip", "ldp_engine_phased.cpp", "ldp_phased_ld.cpp")]
 
 
@@ -140,7 +141,7 @@ def build_library(force=False, verbose=False, measure=False):
     without a GPU).  In-tree so the .so travels with the repo snapshot.  One object per source under lib/_obj/, stale ones
     recompiled in parallel, then one link.  measure=True: the measurement build, lib/libldprune_hip_measure.so (-DLDP_MEASURE)."""
     headers = [os.path.join(CSRC, "ldp_device.h"), os.path.join(CSRC, "ldp_pair_device.h"), os.path.join(CSRC, "ldp_mfma_device.h"),
-               os.path.join(CSRC, "ldp_env.h"), os.path.join(CSRC, "ldp_engine_internal.h"), os.path.join(CSRC, "ldp_compact_schedule.h"),
+               os.path.join(CSRC, "ldp_env.h"), os.path.join(CSRC, "ldp_engine_internal.h"), os.path.join(CSRC, "ldp_compact_schedule.h"), os.path.join(CSRC, "ldp_hwe_core.h"),
                os.path.join(REPO, "include", "ldprune_hip.h"), os.path.join(REPO, "include", "ldprune_hip_debug.h")]
     headers = [h for h in headers if os.path.exists(h)]
     lib_path = MEASURE_LIB_PATH if measure else LIB_PATH
@@ -246,6 +247,12 @@ def lib():
     L.ldp_debug_get_sample_missing_stats.argtypes = [vp, f64p, u64p]
     L.ldp_sample_het_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), u64p, u32p, u32p, u64p]
     L.ldp_debug_sample_het_counts.argtypes = L.ldp_sample_het_counts.argtypes + [ctypes.c_uint32, f64p, u64p]
+    L.ldp_hwe_ln_pvals.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, f64p, ctypes.POINTER(ctypes.c_uint8)]
+    L.ldp_debug_hwe_ln_pvals.argtypes = L.ldp_hwe_ln_pvals.argtypes + [f64p]
+    L.ldp_hwe_ln_pvals_counts.argtypes = [ctypes.c_int, ctypes.c_uint32, u32p, u32p, u32p, ctypes.c_int, f64p, ctypes.POINTER(ctypes.c_uint8)]
+    L.ldp_debug_hwe_ln_pvals_counts.argtypes = L.ldp_hwe_ln_pvals_counts.argtypes + [f64p]
+    L.ldp_hwe_ln_p_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]
+    L.ldp_hwe_ln_p_host.restype = ctypes.c_double
     L.ldp_load_pgen_records.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
                                         ctypes.POINTER(ldp_pgen_rec), ctypes.c_uint32, u32p]
     L.ldp_load_pgen_records_phased.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ldp_pgen_rec),
@@ -370,6 +377,40 @@ def phased_ld(stats):
     if rc != LDP_OK:
         raise LdpError(rc, "ldp_phased_ld failed")
     return tuple(a[:n].reshape(st.shape) for a in (r2, d, dp, neg))
+
+
+def _hwe_counts(hom1, het, hom2):
+    cts = [np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.uint32) for a in (hom1, het, hom2)]
+    if not (cts[0].size == cts[1].size == cts[2].size):
+        raise ValueError("hom1, het and hom2 need one entry per variant each")
+    return cts
+
+
+def hwe_ln_pvals_counts(hom1, het, hom2, midp=False, device=0, stats=None):
+    """ldp_hwe_ln_pvals_counts: the exact Hardy-Weinberg test of every (hom1, het, hom2) triple on the device.  Returns (ln_p, flags):
+    float64 / uint8 arrays (flags bit 0: a tolerance tie was met).  stats (a dict that receives 'ms_kernel') takes the call through
+    ldp_debug_hwe_ln_pvals_counts."""
+    a, b, c = _hwe_counts(hom1, het, hom2)
+    n = a.size
+    ln_p, flags = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.uint8)
+    pad = [x if n else np.zeros(1, dtype=np.uint32) for x in (a, b, c)]
+    args = [int(device), n] + [_ptr(x, ctypes.c_uint32) for x in pad] + [int(bool(midp)), _ptr(ln_p, ctypes.c_double), _ptr(flags, ctypes.c_uint8)]
+    if stats is None:
+        rc = lib().ldp_hwe_ln_pvals_counts(*args)
+    else:
+        ms = ctypes.c_double()
+        rc = lib().ldp_debug_hwe_ln_pvals_counts(*(args + [ctypes.byref(ms)]))
+        stats.update(ms_kernel=float(ms.value))
+    if rc != LDP_OK:
+        raise LdpError(rc, "ldp_hwe_ln_pvals_counts failed")
+    return ln_p[:n], flags[:n]
+
+
+def hwe_ln_p_host(hom1, het, hom2, midp=False):
+    """ldp_hwe_ln_p_host: the same arithmetic for one triple on the calling thread (no GPU).  Returns (ln_p, flags)."""
+    f = ctypes.c_uint8()
+    v = lib().ldp_hwe_ln_p_host(int(hom1), int(het), int(hom2), int(bool(midp)), ctypes.byref(f))
+    return float(v), int(f.value)
 
 
 def synth_genotypes_host(seed, first_variant, n_variants, founder_ct, missing_rate=0.0):
@@ -928,6 +969,21 @@ class LdPruneEngine:
             if stats is not None:
                 stats.update(ms_kernel=float(ms.value), bytes_read=int(nb.value))
         return het[:self.founder_ct], mis[:self.founder_ct], (None if mw is None else mw[:self.founder_ct])
+
+    def hwe_ln_pvals(self, first=0, n=None, midp=False, stats=None):
+        """ldp_hwe_ln_pvals: the exact Hardy-Weinberg test of the variants of [first, first + n), from the genotype counts in the records on
+        the device.  Returns (ln_p, flags): float64 / uint8 arrays of n entries (flags bit 0: a tolerance tie was met).  stats (a dict that
+        receives 'ms_kernel') takes the call through ldp_debug_hwe_ln_pvals."""
+        n = self.variant_ct - first if n is None else n
+        ln_p, flags = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.uint8)
+        if stats is None:
+            self._ck(self._L.ldp_hwe_ln_pvals(self._h, int(first), int(n), int(bool(midp)), _ptr(ln_p, ctypes.c_double), _ptr(flags, ctypes.c_uint8)))
+        else:
+            ms = ctypes.c_double()
+            self._ck(self._L.ldp_debug_hwe_ln_pvals(self._h, int(first), int(n), int(bool(midp)), _ptr(ln_p, ctypes.c_double), _ptr(flags, ctypes.c_uint8),
+                                                    ctypes.byref(ms)))
+            stats.update(ms_kernel=float(ms.value))
+        return ln_p[:n], flags[:n]
 
     def release_device(self):
         """Free the engine's device memory, keep its plan (ldp_release_device)."""

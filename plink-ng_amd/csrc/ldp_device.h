@@ -420,6 +420,11 @@ hipError_t launch_sample_missing(const uint8_t* codes, uint64_t pitch, uint64_t 
 // over the included rows; include (NULL: all) / weight: device arrays of n_rows entries
 hipError_t launch_sample_het(const uint8_t* codes, uint64_t pitch, uint64_t row0, uint32_t n_rows, uint32_t founder_ct, const uint8_t* include, const uint64_t* weight,
                              uint32_t* het_ct, uint32_t* missing_ct, uint64_t* missing_weight, uint32_t slab_rows_opt, hipStream_t stream);
+// ldp_hwe.hip: ln_p[v], flags[v] = the exact Hardy-Weinberg test (ldp_hwe_core.h) of variant v < n, its counts read from recs[v] (n_homref, n_het,
+// n_homalt) or, recs NULL, from hom1[v], het[v], hom2[v]; all device arrays.  A triple summing to 2^31 or more: NaN and kHweFlagInvalid
+constexpr uint8_t kHweFlagInvalid = 0x80;
+hipError_t launch_hwe(const ldp_variant_rec* recs, const uint32_t* hom1, const uint32_t* het, const uint32_t* hom2, uint32_t n, int midp, double* ln_p, uint8_t* flags,
+                      hipStream_t stream);
 hipError_t launch_pair_stats_ref_codes(const uint8_t* codes, uint64_t code_row_bytes, const ldp_variant_rec* recs, const uint32_t* first, const uint32_t* second,
                                        uint32_t n_pairs, ldp_pair_stats_t* out, hipStream_t stream);
 constexpr double kSmallEpsilon = 0.00000000000005684341886080801486968994140625;  // 2^-44 (plink2_float.h:119)

@@ -833,6 +833,78 @@ bool parse_report_flags(Args& A, ArgCursor& c, const std::string& f) {
     A.het = true;
     return true;
   }
+  // (a token that starts with '-' and goes on with a digit or '.' is a number, not a flag: plink2_cmdline.cc IsCmdlineFlagStart)
+  auto is_param = [](const char* t) { return (t[0] != '-') || ((t[1] >= '0') && (t[1] <= '9')) || (t[1] == '.'); };
+  if (f == "--hardy") {  // plink2.cc:6986-7023: ['zs'] ['midp'] ['log10'] ['redundant'] ['cols='...], at most five
+    std::vector<std::string> mods;
+    while ((i + 1 < argc) && is_param(argv[i + 1])) {
+      mods.push_back(argv[++i]);
+    }
+    if (mods.size() > 5) {
+      die(8, "Error: --hardy accepts at most 5 arguments.\n");
+    }
+    for (const std::string& m : mods) {
+      if (m == "zs") {
+        A.hardy_zs = true;
+      } else if (m == "midp") {
+        A.hardy_midp = true;
+      } else if ((m == "log10") || (m == "redundant") || (m.compare(0, 5, "cols=") == 0)) {
+        die(63, "Error: the '%s' modifier of --hardy is not supported by plink2-hip (default columns, 'zs', 'midp' only).\n", m.c_str());
+      } else {
+        die(8, "Error: Invalid --hardy argument '%s'.\n", m.c_str());
+      }
+    }
+    A.hardy = true;
+    return true;
+  }
+  if (f == "--hwe") {  // plink2.cc:7024-7077: <p-value threshold> [sample-size term] ['midp'] ['keep-fewhet'], in any order
+    std::vector<std::string> mods;
+    while ((i + 1 < argc) && is_param(argv[i + 1])) {
+      mods.push_back(argv[++i]);
+    }
+    if (mods.empty()) {
+      die(8, "Error: Missing --hwe argument.\n");
+    }
+    if (mods.size() > 4) {
+      die(8, "Error: --hwe accepts at most 4 arguments.\n");
+    }
+    bool thresh_seen = false;
+    for (const std::string& m : mods) {
+      if (m == "midp") {
+        A.hwe_midp = true;
+      } else if (m == "keep-fewhet") {
+        A.hwe_keep_fewhet = true;
+      } else if (!thresh_seen) {
+        const char* endp = scan_ln(m.c_str(), &A.hwe_ln_thresh);
+        if ((!endp) || *endp) {
+          die(8, "Error: Invalid --hwe argument sequence.\n");
+        }
+        if (A.hwe_ln_thresh > 0.0) {
+          die(8, "Error: Invalid --hwe threshold '%s' (must be in [0, 1]).\n", m.c_str());
+        }
+        thresh_seen = true;
+      } else {
+        const char* endp = m.c_str();
+        if ((A.hwe_sample_size_term != -1) || (!scan_double_plink(m.c_str(), &A.hwe_sample_size_term, &endp)) || *endp) {
+          die(8, "Error: Invalid --hwe argument sequence.\n");
+        }
+        if (A.hwe_sample_size_term < 0.0) {
+          die(8, "Error: Invalid --hwe sample size term '%s' (must be nonnegative).\n", m.c_str());
+        }
+      }
+    }
+    if (!thresh_seen) {
+      die(8, "Error: No --hwe p-value threshold specified.\n");
+    }
+    if ((A.hwe_ln_thresh == 0.0) && (A.hwe_sample_size_term < 1.1102230246251565e-16)) {  // (2^-53)
+      die(8, "Error: --hwe threshold cannot be 1 unless a nonzero sample size term is\nspecified.\n");
+    }
+    if (A.hwe_midp && (A.hwe_ln_thresh >= -0.6931471805599453)) {
+      die(8, "Error: --hwe threshold must be smaller than 0.5 when using mid-p adjustment.\n");
+    }
+    A.hwe = true;
+    return true;
+  }
   if (f == "--bad-freqs") {
     A.bad_freqs = true;
     return true;
@@ -916,7 +988,7 @@ void check_flag_combinations(Args& A) {
   } else if (A.clump_unphased) {
     die(8, "Error: --clump-unphased must be used with --clump.\n");
   }
-  if (!A.have_prune && !A.have_r2 && !A.any_report() && !A.het) {
+  if (!A.have_prune && !A.have_r2 && !A.any_report() && !A.het && !A.hardy) {
     die(8, "Error: no command given (plink2-hip implements --indep-pairwise and --r2-unphased matrices).\n");
   }
   if (A.have_prune && (A.parallel_tot != 1)) {

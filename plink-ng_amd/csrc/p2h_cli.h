@@ -46,6 +46,7 @@ bool scan_double_plink(const char* s, double* out, const char** endp);
 uint32_t banker_round(double v);  // v >= 0, < 2^31
 char* put_digits_trimmed(uint32_t u, int digits, int keep, char* out);
 char* format_g6(double x, char* out);
+char* format_ln_g6(double ln_val, char* out);  // exp(ln_val) as the reference prints p-values (p2h_clump.cpp)
 
 // Output file, optionally Zstandard-compressed ('zs': <name>.zst, as the reference's compress stream writes it;
 // plink2_compress_stream.cc).  libzstd.so.1 is bound by hand (no zstd headers in the image); the default compression
@@ -219,6 +220,11 @@ struct Args {
   bool rep_vmiss() const { return rep_missing && !rep_sample_only; }
   // --het ['zs'] ['small-sample'] (p2h_het.cpp): after every filter, over the variants they leave -- a command of its own or beside any other
   bool het = false, het_zs = false, het_small_sample = false;
+  // --hwe <p> [<k>] ['midp'] ['keep-fewhet'] (a count filter between --geno and --maf / --mac: CountFilters) and its report --hardy ['zs'] ['midp']
+  // (p2h_reports.cpp: write_hardy), over what --geno leaves; ln of the threshold as the reference scans it, sample-size term -1 = not given
+  bool hwe = false, hwe_midp = false, hwe_keep_fewhet = false;
+  double hwe_ln_thresh = 0.0, hwe_sample_size_term = -1.0;
+  bool hardy = false, hardy_zs = false, hardy_midp = false;
   bool bad_freqs = false;  // --bad-freqs: --het may estimate allele frequencies from fewer than 50 founders (plink2.cc:2076)
   bool timing = false;    // --timing: print per-phase wall times
   bool dry_run = false;  // parse + plan only, print the parameters exactly (%a) and exit: used by the CPU tests
@@ -573,6 +579,9 @@ struct Session {
   bool het_device = false;
   const char* het_host_reason = nullptr;
   std::vector<uint32_t> report_variants;
+  // --hwe / --hardy on the host's pass: seconds spent in ldp_hwe_ln_p_host on the reader's threads, p-values computed, tolerance ties among them
+  double hwe_host_s = 0.0;
+  uint32_t hwe_host_ct = 0, hwe_host_ties = 0;
   double t_begin_first = 0.0;            // restarted run: main()'s first start (the total of --timing covers both loads)
   // (... and, once the runtime is up, this thread -- the one that creates the engines, their copy threads and their pinned staging -- moves next to the device)
   void join_hip() {
@@ -601,17 +610,39 @@ struct Session {
 // the rows (load_inputs) and the records of the engine's own count pass (run_prune: ldp_get_variant_recs, then ldp_restrict_variants).
 struct CountFilters {
   const Args& A;
-  bool geno_on, mac_on, freq_on;
+  bool geno_on, mac_on, freq_on, hwe_on;
   uint32_t missing_max;
   double min_maf, max_maf;
-  uint32_t geno_removed = 0, freq_removed = 0;
+  double hwe_ln_base, hwe_coeff;  // --hwe: a variant with n calls goes when ln p < hwe_ln_base + n * hwe_coeff (EnforceHweThresh, plink2_filter.cc:3539)
+  uint32_t geno_removed = 0, hwe_removed = 0, freq_removed = 0;
+  uint32_t hwe_min_obs = 0xffffffffu, hwe_max_obs = 0;  // over the variants --hwe computed a p-value for
   CountFilters(const Args& args, uint32_t kept_samples);
-  bool any() const { return geno_on || freq_on; }
-  // true: the variant goes (and is counted under the filter that removed it).  missing: calls missing among the kept samples; ref2 / het /
-  // alt2: the founders' genotype counts; dosage: their (ref, alt) dosage sums in 16384ths of a copy when the record has a dosage track
-  bool drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t alt2, const std::pair<uint64_t, uint64_t>* dosage = nullptr);
-  void log_counts() const;  // the reference's two log lines
+  bool any() const { return geno_on || hwe_on || freq_on; }
+  bool fails_geno(uint32_t missing) const { return geno_on && (missing > missing_max); }
+  // true: the variant goes (and is counted under the filter that removed it), --geno first, then --hwe, then the frequency filters.  missing:
+  // calls missing among the kept samples; ref2 / het / alt2: the founders' genotype counts; dosage: their (ref, alt) dosage sums in 16384ths
+  // of a copy when the record has a dosage track; hwe_ln_p: ln of the variant's Hardy-Weinberg p-value under --hwe's `midp` setting (from
+  // hwe_kernel or ldp_hwe_ln_p_host), nullptr = --hwe does not test the variant (chrY / MT)
+  bool drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t alt2, const std::pair<uint64_t, uint64_t>* dosage = nullptr, const double* hwe_ln_p = nullptr);
+  // the reference's log lines in its order: --geno's, whatever `after_geno` logs (--hardy's report), --hwe's -- with its warning about
+  // observation counts, or its error about a threshold too strict for the sample size (exit 7) --, the frequency filters'
+  void log_counts(const std::function<void()>& after_geno = nullptr) const;
 };
+// --hardy: what the one writer takes, whichever pass counted (p2h_reports.cpp)
+struct HardyCounts {
+  std::vector<uint32_t> variants;            // raw index of every listed variant: what --geno leaves, chrX / chrY / MT apart
+  std::vector<uint32_t> hom1, het, hom2;     // the founders' genotype counts (REF/REF, REF/ALT, ALT/ALT)
+  std::vector<double> ln_p;                  // under --hardy's `midp` setting
+  uint32_t haploid_skipped = 0;              // chrY / MT variants left out (the reference says how many)
+  void add(uint32_t v, uint32_t a, uint32_t b, uint32_t c, double lp) {
+    variants.push_back(v);
+    hom1.push_back(a);
+    het.push_back(b);
+    hom2.push_back(c);
+    ln_p.push_back(lp);
+  }
+};
+void write_hardy(const Session& S, const HardyCounts& H);
 // Why a job's count filters cannot be decided from the device's records (nullptr: they can).  The image holds founder columns only and
 // --geno counts over the kept samples; one engine holds every row only with one GPU; the r^2 outputs, --clump and --indep-pairphase keep
 // the host's pass (their engines are planned before the load); dosage-based frequencies never reach the device.

@@ -227,12 +227,31 @@ CountFilters::CountFilters(const Args& args, uint32_t kept_samples) : A(args) {
   missing_max = static_cast<uint32_t>(static_cast<int32_t>(A.geno * (1 + kSmallEpsilon) * static_cast<double>(kept_samples)));
   min_maf = A.min_maf * (1.0 - kSmallEpsilon);
   max_maf = A.max_maf * (1.0 + kSmallEpsilon);
+  // (a run of --hardy alone: the reference applies --geno, which the report depends on, and none of the filters behind the report)
+  const bool consumer = A.have_prune || A.have_r2 || A.het;
+  freq_on = freq_on && consumer;
+  hwe_on = A.hwe && consumer;
+  hwe_ln_base = A.hwe_ln_thresh * (1 + kSmallEpsilon);
+  hwe_coeff = (A.hwe_sample_size_term <= 0) ? 0.0 : (A.hwe_sample_size_term * -2.3025850929940457);
 }
 
-bool CountFilters::drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t alt2, const std::pair<uint64_t, uint64_t>* dosage) {
+bool CountFilters::drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t alt2, const std::pair<uint64_t, uint64_t>* dosage, const double* hwe_ln_p) {
   if (geno_on && (missing > missing_max)) {
     ++geno_removed;
     return true;
+  }
+  if (hwe_on && hwe_ln_p) {
+    // EnforceHweThresh (plink2_filter.cc:3604-3623, :3688-3695): nobody called = kept and not counted as an observation; keep-fewhet spares
+    // a variant without het excess before any p-value is looked at
+    const uint64_t obs = ref2 + het + alt2;
+    if (obs && !(A.hwe_keep_fewhet && (het * het <= 4 * ref2 * alt2))) {
+      hwe_min_obs = std::min(hwe_min_obs, static_cast<uint32_t>(obs));
+      hwe_max_obs = std::max(hwe_max_obs, static_cast<uint32_t>(obs));
+      if (*hwe_ln_p < hwe_ln_base + static_cast<double>(obs) * hwe_coeff) {
+        ++hwe_removed;
+        return true;
+      }
+    }
   }
   if (freq_on) {
     // allele counts in 16384ths of a copy: the hardcalls', or -- a record with dosages -- the founders' dosage sums
@@ -262,9 +281,25 @@ bool CountFilters::drops(uint32_t missing, uint64_t ref2, uint64_t het, uint64_t
   return false;
 }
 
-void CountFilters::log_counts() const {
+void CountFilters::log_counts(const std::function<void()>& after_geno) const {
   if (geno_on) {
     logprintf("--geno: %u variant%s removed due to missing genotype data.\n", geno_removed, (geno_removed == 1) ? "" : "s");
+  }
+  if (after_geno) {
+    after_geno();
+  }
+  if (hwe_on) {  // plink2_filter.cc:3697-3710
+    const char* midp = A.hwe_midp ? " midp" : "";
+    const char* fewhet = A.hwe_keep_fewhet ? " keep-fewhet" : "";
+    if ((A.hwe_sample_size_term == -1) && (!A.hwe_keep_fewhet) && (static_cast<double>(hwe_max_obs) * 0.0005 * -2.3025850929940457 < hwe_ln_base)) {
+      logprintf("Error: --hwe filter is suspiciously strict for the sample size; you may be\nfiltering out many variants with association signals.\n");
+      logprintf_ww("If you are performing routine QC, consider using --hwe with a sample-size term (e.g. \"--hwe 1e-5 0.001%s\" results in a threshold of 1e-6 with 1000 observations, 1e-7 with 2000 observations, etc.), and/or specifying 'keep-fewhet' to remove only variants with heterozygosity excess.\n", midp);
+      die(7, "Alternatively, if the strictness is intentional (e.g. you are preparing data\nfor a method that requires variants to be near Hardy-Weinberg equilibrium),\nexplicitly specify a sample-size term of 0.\n");
+    } else if ((A.hwe_sample_size_term <= 0) && (static_cast<uint64_t>(hwe_max_obs) * 9 > static_cast<uint64_t>(hwe_min_obs) * 10)) {
+      // ("10%.0 Consider": what the reference's own format string, which leaves its percent sign unescaped, prints through glibc)
+      logprintf_ww("Warning: --hwe observation counts vary by more than 10%%.0 Consider using --hwe with a sample-size term (e.g. \"--hwe 1e-5 0.001%s%s\" results in a threshold of 1e-6 with 1000 observations, 1e-7 with 2000 observations, etc.), and/or filtering out high-missingness variants with --geno.\n", midp, fewhet);
+    }
+    logprintf_ww("--hwe%s%s: %u variant%s removed due to Hardy-Weinberg exact test (founders only).\n", midp, fewhet, hwe_removed, (hwe_removed == 1) ? "" : "s");
   }
   if (freq_on) {
     logprintf("%u variant%s removed due to allele frequency threshold(s)\n(--maf/--max-maf/--mac/--max-mac).\n", freq_removed, (freq_removed == 1) ? "" : "s");
@@ -275,7 +310,7 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
   if (g_dbg.host_filter) {
     return "--debug-host-filter";
   }
-  if (((!A.have_prune) && (A.have_r2 || !(A.any_report() || A.het))) || A.pairphase) {  // (a run of reports or of --het alone loads like the prune)
+  if (((!A.have_prune) && (A.have_r2 || !(A.any_report() || A.het || A.hardy))) || A.pairphase) {  // (a run of reports, of --het or of --hardy alone loads like the prune)
     return A.pairphase ? "--indep-pairphase plans its engines before the load" : "the r^2 outputs and --clump plan their engines before the load";
   }
   if (A.gpus != 1) {
@@ -1002,9 +1037,12 @@ void load_inputs(Session& S, int argc, char** argv) {
   if (A.het) {
     het_stage(S, chr_filter, extract_ids, exclude_ids);
   }
-  if ((freq_filter || (A.geno != 1.0)) && (A.have_prune || A.have_r2 || A.het)) {
-    std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome
+  const bool hwe_any = A.hwe || A.hardy;
+  if ((freq_filter || (A.geno != 1.0) || hwe_any) && (A.have_prune || A.have_r2 || A.het || A.hardy)) {
+    std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chrX, 4 = chrY / MT (--hwe / --hardy alone: neither tested nor listed)
     std::vector<uint32_t> todo;
+    std::vector<uint8_t> todo_haploid;
+    uint32_t haploid_ct = 0;
     for (uint32_t v = 0; v < raw_variant_ct; ++v) {
       auto it = chr_state.find(V.chrom[v]);
       if (it == chr_state.end()) {
@@ -1014,21 +1052,29 @@ void load_inputs(Session& S, int argc, char** argv) {
                                          (A.autosome && !((code >= 1) && (code <= 22))));
         bool zero = false;
         const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
-        if ((!out) && (cls >= 3)) {
+        if ((!out) && (cls >= 3) && (freq_filter || (A.geno != 1.0))) {
           die(63, "Error: --maf / --max-maf / --mac / --max-mac / --geno on chrX, chrY or MT ('%s') are not supported by plink2-hip: filter them out (--autosome, --chr) or pre-filter with plink2.\n", cur.c_str());
         }
-        it = chr_state.emplace(cur, static_cast<uint8_t>(out)).first;
+        it = chr_state.emplace(cur, static_cast<uint8_t>((out ? 1 : 0) | ((cls == 3) ? 2 : 0) | ((cls > 3) ? 4 : 0))).first;
       }
-      if (it->second || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
+      if ((it->second & 1) || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
         continue;
       }
       if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
         continue;
       }
+      if (it->second & 2) {  // (.hardy.x and the joint test of females' genotypes and males' alleles are not built)
+        die(63, "Error: --hwe / --hardy with a chrX variant ('%s') are not supported by plink2-hip: filter chrX out (--autosome, --not-chr) or use plink2.\n", V.id[v].c_str());
+      }
       if (V.alt_ct[v] > 1) {
+        if (hwe_any) {  // (one test per allele against the rest, on genotype counts nobody makes here)
+          die(63, "Error: --hwe / --hardy with a multiallelic variant ('%s') are not supported by plink2-hip: --max-alleles 2 leaves them out.\n", V.id[v].c_str());
+        }
         die(63, "Error: --maf / --max-maf / --mac / --max-mac / --geno with multiallelic variants ('%s') are not supported by plink2-hip.\n", V.id[v].c_str());
       }
       todo.push_back(v);
+      todo_haploid.push_back((it->second & 4) ? 1 : 0);
+      haploid_ct += (it->second & 4) ? 1u : 0u;
     }
     const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
     std::vector<uint64_t> m_f(words, 0), m_s(words, 0);
@@ -1048,6 +1094,9 @@ void load_inputs(Session& S, int argc, char** argv) {
     S.count_filters = true;
     S.kept_sample_ct = kept_samples;
     S.host_filter_reason = device_filter_refusal(A, S.has_dosage, kept_samples, founder_ct);
+    if ((!S.host_filter_reason) && haploid_ct) {
+      S.host_filter_reason = "chrY / MT variants among the kept ones (--hwe / --hardy leave them alone; the device's pass takes autosomes only)";
+    }
     if (A.dry_run) {
       logprintf("dry-run: variant filters: %s%s\n", S.host_filter_reason ? "host pass: " : "from the device's count pass", S.host_filter_reason ? S.host_filter_reason : "");
     }
@@ -1071,15 +1120,69 @@ void load_inputs(Session& S, int argc, char** argv) {
       }
       drop_by_counts.assign(raw_variant_ct, 0);
       CountFilters F(A, kept_samples);
+      // --hwe / --hardy: ln p of every diploid variant --geno leaves, from the founders' counts, on the reader's threads (ldp_hwe_ln_p_host:
+      // hwe_kernel's arithmetic on the CPU); one set of values serves both where their `midp` settings agree
+      std::vector<double> ln_hwe, ln_hardy;
+      if (hwe_any) {
+        const double t_hwe0 = now_s();
+        const bool two = A.hwe && A.hardy && (A.hwe_midp != A.hardy_midp);
+        const int midp_first = A.hwe ? (A.hwe_midp ? 1 : 0) : (A.hardy_midp ? 1 : 0);
+        ln_hwe.assign(todo.size(), 0.0);
+        if (two) {
+          ln_hardy.assign(todo.size(), 0.0);
+        }
+        std::vector<uint8_t> tie(todo.size(), 0);
+        std::atomic<size_t> next(0);
+        std::vector<std::thread> pool;
+        for (uint32_t t = 0; t < nthreads; ++t) {
+          pool.emplace_back([&]() {
+            for (size_t q0 = next.fetch_add(64); q0 < todo.size(); q0 = next.fetch_add(64)) {
+              for (size_t q = q0; q < std::min(todo.size(), q0 + 64); ++q) {
+                const RowCounts& c = counts[q];
+                if (todo_haploid[q] || F.fails_geno(c.missing)) {
+                  continue;
+                }
+                uint8_t fl = 0, fl2 = 0;
+                ln_hwe[q] = ldp_hwe_ln_p_host(static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), midp_first, &fl);
+                if (two) {
+                  ln_hardy[q] = ldp_hwe_ln_p_host(static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), A.hardy_midp ? 1 : 0, &fl2);
+                }
+                tie[q] = static_cast<uint8_t>(1 | (((fl | fl2) & 1) << 1));
+              }
+            }
+          });
+        }
+        for (std::thread& th : pool) {
+          th.join();
+        }
+        for (uint8_t x : tie) {
+          S.hwe_host_ct += x & 1;
+          S.hwe_host_ties += x >> 1;
+        }
+        S.hwe_host_s = now_s() - t_hwe0;
+        if (A.timing) {  // (here, not with the pass's own timing: --hwe's strictness error ends the run before that)
+          logprintf("[timing] --hwe / --hardy: host pass (%u p-values from ldp_hwe_ln_p_host on %u threads, %.3f s; %u with a tolerance tie)\n", S.hwe_host_ct, nthreads, S.hwe_host_s,
+                    S.hwe_host_ties);
+        }
+      }
+      HardyCounts H;
+      H.haploid_skipped = haploid_ct;
       for (size_t q = 0; q < todo.size(); ++q) {
         const RowCounts& c = counts[q];
+        if (A.hardy && (!todo_haploid[q]) && !F.fails_geno(c.missing)) {
+          H.add(todo[q], static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), ln_hardy.empty() ? ln_hwe[q] : ln_hardy[q]);
+        }
         // (a record with dosages: the founders' dosage sums instead of the hardcalls' allele counts)
         const auto dd = S.dosage_sums.find(todo[q]);
-        if (F.drops(c.missing, c.ref2, c.het, c.alt2, (dd != S.dosage_sums.end()) ? &dd->second : nullptr)) {
+        if (F.drops(c.missing, c.ref2, c.het, c.alt2, (dd != S.dosage_sums.end()) ? &dd->second : nullptr, (hwe_any && !todo_haploid[q]) ? &ln_hwe[q] : nullptr)) {
           drop_by_counts[todo[q]] = 1;
         }
       }
-      F.log_counts();
+      F.log_counts([&]() {
+        if (A.hardy) {
+          write_hardy(S, H);
+        }
+      });
       S.host_filter_s = now_s() - t_filter0;
       if (A.timing) {
         logprintf("[timing] variant filters: host pass (%.3f s; %s)\n", S.host_filter_s, S.host_filter_reason ? S.host_filter_reason : "--dry-run");

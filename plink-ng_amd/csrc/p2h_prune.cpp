@@ -79,6 +79,10 @@ struct PruneJob {
   // the count filters decided from the engine's records (Session::device_filter)
   uint64_t filter_rows_compacted = 0, filter_rows_bounced = 0;
   double filter_ms_compact = 0.0, filter_s = 0.0, filter_ms_recount = 0.0;
+  // --hwe / --hardy from the same records (filter_on_device): p-values computed, hwe_kernel's time, variants whose flag byte names a tolerance tie
+  double hwe_ms_kernel = 0.0;
+  uint64_t hwe_pvals = 0;
+  uint32_t hwe_ties = 0;
   int world = 1, n_devices = 1;
   bool alias_devices = false;
   std::vector<ldp_engine*> eng;
@@ -958,11 +962,42 @@ struct PruneJob {
       die(16, "\nError: %s\n", ldp_last_error(eng[0]));
     }
     CountFilters F(A, S.kept_sample_ct);
+    // --hwe / --hardy: ln p of every row from the same records, where they lie (hwe_kernel through ldp_hwe_ln_pvals: no copy of the records,
+    // no host thread); one call serves both where their `midp` settings agree.  (--timing: the call through its measurement hook)
+    std::vector<double> ln_hwe, ln_hardy;
+    if (A.hwe || A.hardy) {
+      const int midp_first = A.hwe ? (A.hwe_midp ? 1 : 0) : (A.hardy_midp ? 1 : 0);
+      std::vector<uint8_t> flags(std::max<uint32_t>(m_ct, 1), 0);
+      auto pvals = [&](int midp, std::vector<double>* out) {
+        out->assign(std::max<uint32_t>(m_ct, 1), 0.0);
+        double ms = 0.0;
+        if (ldp_debug_hwe_ln_pvals(eng[0], 0, m_ct, midp, out->data(), flags.data(), &ms)) {
+          die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+        }
+        hwe_ms_kernel += ms;
+        hwe_pvals += m_ct;
+        for (uint32_t q = 0; q < m_ct; ++q) {
+          hwe_ties += flags[q] & 1;
+        }
+      };
+      pvals(midp_first, &ln_hwe);
+      if (A.hwe && A.hardy && (A.hwe_midp != A.hardy_midp)) {
+        pvals(A.hardy_midp ? 1 : 0, &ln_hardy);
+      }
+      if (A.timing) {  // (here, not with the other filter timings: --hwe's strictness error ends the run before those)
+        logprintf("[timing] --hwe / --hardy: from the device's records (%llu p-values, hwe_kernel %.3f ms; %u with a tolerance tie)\n", static_cast<unsigned long long>(hwe_pvals), hwe_ms_kernel,
+                  hwe_ties);
+      }
+    }
+    HardyCounts H;
     std::vector<uint64_t> keep((static_cast<size_t>(m_ct) + 63) / 64 + 1, 0);
     uint32_t kept = 0, chr0_left = 0;
     for (uint32_t q = 0; q < m_ct; ++q) {
       const ldp_variant_rec& r = recs[q];
-      if (!F.drops(founder_ct - r.nm_ct, r.n_homref, r.n_het, r.n_homalt)) {
+      if (A.hardy && !F.fails_geno(founder_ct - r.nm_ct)) {
+        H.add(S.inc[q], r.n_homref, r.n_het, r.n_homalt, ln_hardy.empty() ? ln_hwe[q] : ln_hardy[q]);
+      }
+      if (!F.drops(founder_ct - r.nm_ct, r.n_homref, r.n_het, r.n_homalt, nullptr, ln_hwe.empty() ? nullptr : &ln_hwe[q])) {
         if ((q < S.inc_chr0.size()) && S.inc_chr0[q]) {
           ++chr0_left;  // (never pruned, never listed: LdPrune strips chromosome 0, plink2_ld.cc:2542)
           continue;
@@ -976,7 +1011,11 @@ struct PruneJob {
         ++kept;
       }
     }
-    F.log_counts();
+    F.log_counts([&]() {
+      if (A.hardy) {
+        write_hardy(S, H);
+      }
+    });
     if ((!kept) && !chr0_left) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
       filter_s = now_s() - t0;
       report_filter_timing();
@@ -1022,6 +1061,7 @@ struct PruneJob {
     }
     logprintf("[timing] variant filters: from the device's count pass (%llu rows compacted, %.3f ms; records, filter arithmetic and the new plan %.3f s in all)\n",
               static_cast<unsigned long long>(filter_rows_compacted), filter_ms_compact, filter_s);
+
     if ((founder_ct <= ldp_matrix_pipe_max_founders()) && (filter_ms_compact > 0.0) && (filter_ms_recount > 0.0)) {
       // image rows of ceil(founders / 512) x 128 bytes: the compaction reads and writes a moved row once, twice when its batch goes through the bounce
       // buffer (few rows dropped in front of it); the count pass reads the kept rows
@@ -1365,7 +1405,7 @@ struct PruneJob {
   }
 
   int run() {
-    if ((!A.have_prune) && (!S.report_device) && !(A.het && S.device_filter)) {
+    if ((!A.have_prune) && (!S.report_device) && !((A.het || A.hardy) && S.device_filter)) {
       if (A.het) {
         het_host_pass(S);  // (the host's filters made the list final in load_inputs)
       }
@@ -1398,7 +1438,7 @@ struct PruneJob {
       }
       if (S.report_device) {
         reports_on_device();
-        if ((!A.have_prune) && !A.het) {
+        if ((!A.have_prune) && (!A.het) && !A.hardy) {
           S.file_to_hbm_done();
           finish();  // a run of reports alone stops here: no plan, no pair kernel
         }
@@ -1408,7 +1448,9 @@ struct PruneJob {
       }
       if (!A.have_prune) {
         report_filter_timing();
-        het_stage();  // --het alone, after the filters: no band plan, no pair kernel
+        if (A.het) {
+          het_stage();  // --het alone, after the filters: no band plan, no pair kernel
+        }
         S.file_to_hbm_done();
         finish();
       }

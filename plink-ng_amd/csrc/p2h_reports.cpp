@@ -312,4 +312,63 @@ void write_reports(const Session& S, const ReportCounts& C) {
   }
 }
 
+// --hardy (HardyReport, plink2_misc.cc:5397-5687) with its default columns: one line per listed variant, A1 = REF and AX = ALT, the founders'
+// three genotype counts, observed and expected het frequency as the reference forms them (:5641-5655: a variant nobody has a call at
+// prints 0 * (1 / 0) = nan and, its A1 homozygotes being all of its calls, 0), and the p-value printed from its logarithm, so that values
+// far below DBL_MIN print as the reference's do.  No file when nothing is listed.
+void write_hardy(const Session& S, const HardyCounts& H) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  if (H.haploid_skipped) {
+    logprintf("--hardy: Skipping %u haploid variant%s.\n", H.haploid_skipped, (H.haploid_skipped == 1) ? "" : "s");
+  }
+  const size_t n = H.variants.size();
+  if (!n) {
+    return;
+  }
+  const std::string path = A.out + ".hardy" + (A.hardy_zs ? ".zst" : "");
+  OutFile f;
+  f.open(path, A.hardy_zs);
+  char num[64];
+  std::string buf = "#CHROM\tID\tA1\tAX\tHOM_A1_CT\tHET_A1_CT\tTWO_AX_CT\tO(HET_A1)\tE(HET_A1)\t";
+  buf += A.hardy_midp ? "MIDP\n" : "P\n";
+  ChromNames names(V);
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t v = H.variants[q];
+    buf += names.of(v);
+    buf += '\t';
+    buf += V.id[v];
+    buf += '\t';
+    buf += V.ref[v];
+    buf += '\t';
+    buf += V.alt[v];
+    const uint32_t cts[3] = {H.hom1[q], H.het[q], H.hom2[q]};
+    for (uint32_t x : cts) {
+      buf += '\t';
+      buf.append(num, put_u32(x, num));
+    }
+    const uint32_t nonmissing = cts[0] + cts[1] + cts[2];
+    const double recip = 1.0 / static_cast<double>(nonmissing);
+    buf += '\t';
+    buf.append(num, format_g6(static_cast<double>(cts[1]) * recip, num));
+    buf += '\t';
+    if (cts[0] == nonmissing) {
+      buf += '0';
+    } else {
+      const double dbl_maj_freq = static_cast<double>(cts[0] * 2 + cts[1]) * recip;
+      buf.append(num, format_g6(dbl_maj_freq * (1.0 - dbl_maj_freq * 0.5), num));
+    }
+    buf += '\t';
+    buf.append(num, format_ln_g6(H.ln_p[q], num));
+    buf += '\n';
+    if (buf.size() > (1u << 20)) {
+      f.write(buf.data(), buf.size());
+      buf.clear();
+    }
+  }
+  f.write(buf.data(), buf.size());
+  f.close();
+  logprintf_ww("--hardy%s%s: Autosomal Hardy-Weinberg report (founders only) written to %s .\n", A.hardy_zs ? " zs" : "", A.hardy_midp ? " midp" : "", path.c_str());
+}
+
 }  // namespace p2h

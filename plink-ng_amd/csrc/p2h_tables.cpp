@@ -210,7 +210,7 @@ void load_variants(const Args& A, Variants* V) {
   const std::string buf = zst ? slurp_zst(path) : slurp(path);
   bool header = false;
   int c_chrom = 0, c_pos = 3, c_id = 1, c_alt = -1, c_ref = -1, c_cm = -1, c_info = -1;
-  const bool report_alleles = A.rep_freq || A.rep_gcount;  // (.afreq / .acount / .gcount print REF, ALT and, where some REF is provisional, that)
+  const bool report_alleles = A.rep_freq || A.rep_gcount || A.hardy;  // (.afreq / .acount / .gcount print REF, ALT and, where some REF is provisional, that)
   const bool keep_pr = (A.have_r2 && (A.r2_cols & kVcorColRef)) || (A.have_clump && (A.clump_cols & kClumpColRef)) || report_alleles;
   const bool keep_cm = A.have_r2 && (A.ld_cm_radius != -1.0);
   double last_cm = -1.7976931348623157e308;
