@@ -379,6 +379,37 @@ int ldp_sample_missing_counts(ldp_engine* e, uint32_t first_variant, uint32_t n,
  * calls missing. */
 int ldp_sample_het_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, const uint64_t* weight, uint32_t* het_ct, uint32_t* missing_ct,
                           uint64_t* missing_weight);
+/* KING-robust kinship counts of SAMPLE pairs from the resident image, for a host's --make-king-table (CalcKing,
+ * plink2_matrix_calc.cc).  Over the variants v of [first_variant, first_variant + n) with include[v - first_variant] != 0
+ * (include NULL: all of them), for the samples row in [row_first, row_first + row_ct) and col in [col_first, col_first + col_ct),
+ * col < row: hethet = variants where both are heterozygous, het_row_hom_col / hom_row_het_col = one heterozygous and the other
+ * homozygous, homhom = both homozygous, ibs0 = homozygous for different alleles; a variant where either has no call counts
+ * nowhere.  nsnp is the sum of the first four, and
+ *   kinship = 0.5 - (double)(4 ibs0 + het_row_hom_col + hom_row_het_col) / (double)(4 (hethet + min(het_row_hom_col, hom_row_het_col)))
+ * (ComputeKinship; NaN for 0 / 0, -inf for a positive numerator over 0).  Rows and columns are sample indices below founder_ct.
+ * ldp_king_counts_block(): out[(row - row_first) * ld_elems + (col - col_first)] for col < row, zero elsewhere in the block (the
+ * layout of ldp_pair_stats_block()); out: host memory, ld_elems >= col_ct.  ldp_king_block_hits(): the pairs with
+ * !(kinship < min_kinship) -- NaN pairs are kept, -inf pairs are not, as --king-table-filter does -- in no particular order, with
+ * their counts; *count receives their number, which may exceed capacity (the first `capacity` that arrived are stored), as in
+ * ldp_r2_unphased_hits().  The kinship is formed on the device with the division above, correctly rounded: a host that divides the
+ * returned integers gets the same double.  Contract, states and refusals are those of ldp_sample_het_counts(): current indices,
+ * before or after ldp_restrict_variants(); n == 0 gives zeros (and every pair of the block as a hit, its kinship being NaN); the
+ * work runs on the engine's stream, synchronised before the call returns; nothing of the engine changes; LDP_ERR_STATE before
+ * every row of the range is loaded, LDP_ERR_INVALID for a variant range beyond variant_ct, a sample range beyond founder_ct, a
+ * missing output or ld_elems < col_ct, LDP_ERR_UNSUPPORTED on engines that keep bit-planes, on sharded engines, and after
+ * LDP_GENO_PHASED loads or loads through a sample map that makes het calls missing.  Device memory: 20 bytes per pair of the block
+ * (row_ct x col_ct) and at most 128 MiB of scratch while the block has fewer than two million samples. */
+typedef struct {
+  uint32_t hethet, het_row_hom_col, hom_row_het_col, homhom, ibs0;
+} ldp_king_counts_t;
+typedef struct {
+  uint32_t row, col;
+  ldp_king_counts_t c;
+} ldp_king_hit;
+int ldp_king_counts_block(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, uint32_t row_first, uint32_t row_ct, uint32_t col_first, uint32_t col_ct,
+                          ldp_king_counts_t* out, uint64_t ld_elems);
+int ldp_king_block_hits(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, uint32_t row_first, uint32_t row_ct, uint32_t col_first, uint32_t col_ct,
+                        double min_kinship, ldp_king_hit* out, uint64_t capacity, uint64_t* count);
 /* The exact Hardy-Weinberg test of loaded rows, for a host's --hwe / --hardy, from the genotype counts the load's count pass left in the
  * records on the device (n_homref, n_het, n_homalt of ldp_get_variant_recs(); diploid, one ALT allele).  For every variant v of
  * [first_variant, first_variant + n): ln_p[v - first_variant] = the natural logarithm of the test's p-value -- conditional on the

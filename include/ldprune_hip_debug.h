@@ -119,6 +119,14 @@ int ldp_debug_get_sample_missing_stats(const ldp_engine* e, double* ms_kernel, u
 int ldp_debug_sample_het_counts(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, const uint64_t* weight, uint32_t* het_ct, uint32_t* missing_ct,
                                 uint64_t* missing_weight, uint32_t slab_rows, double* ms_kernel, uint64_t* bytes_read);
 
+/* ldp_king_counts_block() with its test and measurement hooks as arguments -- the call keeps no state in the engine --: slab_variants
+ * cuts the variants into slabs of that many (a multiple of 256, at most 65536, otherwise LDP_ERR_INVALID; 0 = chosen from the block's
+ * sample counts so that the strips stay below the scratch cap; results never depend on it); *ms_kernel and *pair_variants (either may
+ * be NULL) receive the device time of the launches (HIP events on the engine's stream) and the pairs of the block times the included
+ * variants. */
+int ldp_debug_king_counts_block(ldp_engine* e, uint32_t first_variant, uint32_t n, const uint8_t* include, uint32_t row_first, uint32_t row_ct, uint32_t col_first,
+                                uint32_t col_ct, ldp_king_counts_t* out, uint64_t ld_elems, uint32_t slab_variants, double* ms_kernel, uint64_t* pair_variants);
+
 /* ldp_hwe_ln_pvals() / ldp_hwe_ln_pvals_counts() with their measurement hook as an argument -- neither keeps state --: *ms_kernel (may be
  * NULL) receives the device time of the hwe_kernel launches (HIP events on the stream they run on). */
 int ldp_debug_hwe_ln_pvals(ldp_engine* e, uint32_t first_variant, uint32_t n, int midp, double* ln_p, uint8_t* flags, double* ms_kernel);

@@ -100,6 +100,8 @@ PHASED_STATS_DTYPE = np.dtype([("valid_obs", "<u4"), ("sum0", "<u4"), ("sum1", "
 CP_SLOT_DTYPE = np.dtype([("a", "<f8"), ("b", "<f8")])
 CP_GEN_SLOT_DTYPE = np.dtype([("nm_r", "<u4"), ("zs_r", "<u4"), ("zq_r", "<u4"), ("pad", "<u4")])
 CP_CHECKPOINTS, CP_GEN_FIRST, CP_GEN_CHECKPOINTS = 5, 2, 2
+KING_COUNTS_DTYPE = np.dtype([("hethet", "<u4"), ("het_row_hom_col", "<u4"), ("hom_row_het_col", "<u4"), ("homhom", "<u4"), ("ibs0", "<u4")])
+KING_HIT_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("hethet", "<u4"), ("het_row_hom_col", "<u4"), ("hom_row_het_col", "<u4"), ("homhom", "<u4"), ("ibs0", "<u4")])
 VARIANT_REC_DTYPE = np.dtype([("nm_ct", "<u4"), ("sum", "<i4"), ("ssq", "<u4"), ("flags", "<u4"), ("n_homref", "<u4"),
                               ("n_het", "<u4"), ("n_homalt", "<u4"), ("reserved", "<u4")])
 
@@ -117,6 +119,7 @@ CABI_SYMBOLS = [
     "ldp_use_private_copy_threads", "ldp_debug_get_pred", "ldp_debug_wide_diag_map", "ldp_get_tile_routes", "ldp_debug_tile_classes",
     "ldp_restrict_variants", "ldp_debug_get_compact_stats", "ldp_sample_missing_counts", "ldp_debug_get_sample_missing_stats",
     "ldp_sample_het_counts", "ldp_debug_sample_het_counts",
+    "ldp_king_counts_block", "ldp_king_block_hits", "ldp_debug_king_counts_block",
     "ldp_hwe_ln_pvals", "ldp_hwe_ln_pvals_counts", "ldp_hwe_ln_p_host", "ldp_debug_hwe_ln_pvals", "ldp_debug_hwe_ln_pvals_counts",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
     "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass", "ldp_get_allele_counts",
@@ -125,7 +128,7 @@ CABI_SYMBOLS = [
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ("ldp_kernels.hip", "ldp_codes.hip", "ldp_pair_mfma.hip", "ldp_pair_wide.hip", "ldp_pred_csr.hip", "ldp_pgen_decode.hip", "ldp_synth.hip", "ldp_engine.cpp", "ldp_engine_run.cpp", "ldp_engine_r2.cpp",
-                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_sample_het.hip", "ldp_engine_sample_het.cpp", "ldp_hwe.hip", "ldp_engine_hwe.cpp", "ldp_hwe_host.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
+                                          "ldp_engine_load.cpp", "ldp_engine_shard.cpp", "ldp_engine_restrict.cpp", "ldp_compact.hip", "ldp_sample_missing.hip", "ldp_engine_sample_missing.cpp", "ldp_sample_het.hip", "ldp_engine_sample_het.cpp", "ldp_king.hip", "ldp_engine_king.cpp", "ldp_hwe.hip", "ldp_engine_hwe.cpp", "ldp_hwe_host.cpp", "ldp_pgen.cpp", "ldp_topology.cpp",
                                           "ldp_pair_phased.hip", "ldp_engine_phased.cpp", "ldp_phased_ld.cpp")]
 
 
@@ -141,7 +144,7 @@ def build_library(force=False, verbose=False, measure=False):
     without a GPU).  In-tree so the .so travels with the repo snapshot.  One object per source under lib/_obj/, stale ones
     recompiled in parallel, then one link.  measure=True: the measurement build, lib/libldprune_hip_measure.so (-DLDP_MEASURE)."""
     headers = [os.path.join(CSRC, "ldp_device.h"), os.path.join(CSRC, "ldp_pair_device.h"), os.path.join(CSRC, "ldp_mfma_device.h"),
-               os.path.join(CSRC, "ldp_env.h"), os.path.join(CSRC, "ldp_engine_internal.h"), os.path.join(CSRC, "ldp_compact_schedule.h"), os.path.join(CSRC, "ldp_hwe_core.h"),
+               os.path.join(CSRC, "ldp_env.h"), os.path.join(CSRC, "ldp_engine_internal.h"), os.path.join(CSRC, "ldp_compact_schedule.h"), os.path.join(CSRC, "ldp_hwe_core.h"), os.path.join(CSRC, "ldp_king_device.h"),
                os.path.join(REPO, "include", "ldprune_hip.h"), os.path.join(REPO, "include", "ldprune_hip_debug.h")]
     headers = [h for h in headers if os.path.exists(h)]
     lib_path = MEASURE_LIB_PATH if measure else LIB_PATH
@@ -178,7 +181,7 @@ def build_library(force=False, verbose=False, measure=False):
 def cli_sources():
     """the front-end's translation units: main() + one unit per concern (csrc/p2h_cli.h is what they share)"""
     return [os.path.join(CSRC, f) for f in ("plink2_hip_cli.cpp", "p2h_util.cpp", "p2h_args.cpp", "p2h_tables.cpp", "p2h_inputs.cpp", "p2h_clump.cpp", "p2h_r2.cpp",
-                                            "p2h_r2_phased.cpp", "p2h_prune.cpp", "p2h_reports.cpp", "p2h_het.cpp")]
+                                            "p2h_r2_phased.cpp", "p2h_prune.cpp", "p2h_reports.cpp", "p2h_het.cpp", "p2h_king.cpp")]
 
 
 def build_cli(force=False, verbose=False):
@@ -247,6 +250,9 @@ def lib():
     L.ldp_debug_get_sample_missing_stats.argtypes = [vp, f64p, u64p]
     L.ldp_sample_het_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), u64p, u32p, u32p, u64p]
     L.ldp_debug_sample_het_counts.argtypes = L.ldp_sample_het_counts.argtypes + [ctypes.c_uint32, f64p, u64p]
+    L.ldp_king_counts_block.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8)] + [ctypes.c_uint32] * 4 + [vp, ctypes.c_uint64]
+    L.ldp_debug_king_counts_block.argtypes = L.ldp_king_counts_block.argtypes + [ctypes.c_uint32, f64p, u64p]
+    L.ldp_king_block_hits.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8)] + [ctypes.c_uint32] * 4 + [ctypes.c_double, vp, ctypes.c_uint64, u64p]
     L.ldp_hwe_ln_pvals.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, f64p, ctypes.POINTER(ctypes.c_uint8)]
     L.ldp_debug_hwe_ln_pvals.argtypes = L.ldp_hwe_ln_pvals.argtypes + [f64p]
     L.ldp_hwe_ln_pvals_counts.argtypes = [ctypes.c_int, ctypes.c_uint32, u32p, u32p, u32p, ctypes.c_int, f64p, ctypes.POINTER(ctypes.c_uint8)]
@@ -969,6 +975,43 @@ class LdPruneEngine:
             if stats is not None:
                 stats.update(ms_kernel=float(ms.value), bytes_read=int(nb.value))
         return het[:self.founder_ct], mis[:self.founder_ct], (None if mw is None else mw[:self.founder_ct])
+
+    def _king_include(self, n, include):
+        if include is None:
+            return None, None
+        include = np.ascontiguousarray(include, dtype=np.uint8)
+        if include.size != n:
+            raise ValueError("include needs one byte per variant of the range")
+        return include, (_ptr(include, ctypes.c_uint8) if n else None)
+
+    def king_counts_block(self, row_first, row_ct, col_first, col_ct, first=0, n=None, include=None, slab_variants=None, stats=None):
+        """ldp_king_counts_block: the five KING-robust integers of the sample pairs col < row of a block over the variants of [first, first + n)
+        whose `include` byte is non-zero (None: all), a (row_ct, col_ct) KING_COUNTS_DTYPE array, zero elsewhere.  slab_variants (variants per
+        slab) or stats (a dict that receives 'ms_kernel' and 'pair_variants') take the call through ldp_debug_king_counts_block."""
+        n = self.variant_ct - first if n is None else n
+        keep, inc_p = self._king_include(n, include)
+        out = np.zeros((max(row_ct, 1), max(col_ct, 1)), dtype=KING_COUNTS_DTYPE)
+        args = [self._h, int(first), int(n), inc_p, int(row_first), int(row_ct), int(col_first), int(col_ct), out.ctypes.data_as(ctypes.c_void_p), out.shape[1]]
+        if (slab_variants is None) and (stats is None):
+            self._ck(self._L.ldp_king_counts_block(*args))
+        else:
+            ms, pv = ctypes.c_double(), ctypes.c_uint64()
+            self._ck(self._L.ldp_debug_king_counts_block(*(args + [int(slab_variants or 0), ctypes.byref(ms), ctypes.byref(pv)])))
+            if stats is not None:
+                stats.update(ms_kernel=float(ms.value), pair_variants=int(pv.value))
+        return out[:row_ct, :col_ct]
+
+    def king_block_hits(self, min_kinship, row_first, row_ct, col_first, col_ct, first=0, n=None, include=None, capacity=1 << 20):
+        """ldp_king_block_hits: the pairs col < row of the block with not (kinship < min_kinship), with their counts: (KING_HIT_DTYPE array
+        sorted by (row, col), number found -- which may exceed capacity)."""
+        n = self.variant_ct - first if n is None else n
+        keep, inc_p = self._king_include(n, include)
+        out = np.zeros(max(capacity, 1), dtype=KING_HIT_DTYPE)
+        found = ctypes.c_uint64()
+        self._ck(self._L.ldp_king_block_hits(self._h, int(first), int(n), inc_p, int(row_first), int(row_ct), int(col_first), int(col_ct), float(min_kinship),
+                                             out.ctypes.data_as(ctypes.c_void_p), int(capacity), ctypes.byref(found)))
+        got = out[:min(found.value, capacity)]
+        return np.sort(got, order=["row", "col"]), int(found.value)
 
     def hwe_ln_pvals(self, first=0, n=None, midp=False, stats=None):
         """ldp_hwe_ln_pvals: the exact Hardy-Weinberg test of the variants of [first, first + n), from the genotype counts in the records on

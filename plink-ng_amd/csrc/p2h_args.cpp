@@ -905,6 +905,65 @@ bool parse_report_flags(Args& A, ArgCursor& c, const std::string& f) {
     A.hwe = true;
     return true;
   }
+  if (f == "--make-king-table") {  // plink2.cc:8530-8598: ['zs'] ['counts'] ['cols='...], at most four
+    std::vector<std::string> mods;
+    while ((i + 1 < argc) && (argv[i + 1][0] != '-')) {
+      mods.push_back(argv[++i]);
+    }
+    if (mods.size() > 4) {
+      die(8, "Error: --make-king-table accepts at most 4 arguments.\n");
+    }
+    for (const std::string& m : mods) {
+      if (m == "zs") {
+        A.king_zs = true;
+      } else if (m == "counts") {
+        A.king_counts = true;
+      } else if ((m == "rel-check") || (m == "concordance-check")) {
+        die(63, "Error: the '%s' modifier of --make-king-table is not supported by plink2-hip ('zs', 'counts', 'cols=' only).\n", m.c_str());
+      } else if (m.compare(0, 5, "cols=") == 0) {
+        if (A.king_cols_given) {
+          die(8, "Error: Multiple --make-king-table cols= modifiers.\n");
+        }
+        A.king_cols = parse_col_descriptor(m.substr(5), {"maybefid", "fid", "id", "maybesid", "sid", "nsnp", "hethet", "ibs0", "ibs1", "ibs", "kinship"}, kKingColDefault,
+                                           "make-king-table");
+        A.king_cols_given = true;
+        if ((!(A.king_cols & kKingColId)) && (A.king_cols & (kKingColMaybefid | kKingColFid | kKingColMaybesid | kKingColSid))) {
+          die(8, "Error: Invalid --make-king-table column set descriptor ('maybefid', 'fid',\n'maybesid', and 'sid' require 'id').\n");
+        }
+      } else if (m == "no-idheader") {
+        die(8, "Error: --make-king-table 'no-idheader' modifier retired.  Use --no-id-header\ninstead.\n");
+      } else {
+        die(8, "Error: Invalid --make-king-table argument '%s'.\n", m.c_str());
+      }
+    }
+    if (!A.king_cols_given) {
+      A.king_cols = kKingColDefault;
+    }
+    A.king = true;
+    return true;
+  }
+  if (f == "--king-table-filter") {  // plink2.cc:7702-7710
+    std::vector<std::string> mods;
+    while ((i + 1 < argc) && ((argv[i + 1][0] != '-') || ((argv[i + 1][1] >= '0') && (argv[i + 1][1] <= '9')) || (argv[i + 1][1] == '.'))) {
+      mods.push_back(argv[++i]);
+    }
+    if (mods.empty()) {
+      die(8, "Error: Missing --king-table-filter argument.\n");
+    }
+    if (mods.size() > 1) {
+      die(8, "Error: --king-table-filter only accepts 1 argument.\n");
+    }
+    const char* endp = mods[0].c_str();
+    if ((!scan_double_plink(mods[0].c_str(), &A.king_filter, &endp)) || *endp || (A.king_filter > 0.5)) {
+      die(8, "Error: Invalid --king-table-filter argument '%s'.\n", mods[0].c_str());
+    }
+    A.king_filter_given = true;
+    return true;
+  }
+  if ((f == "--make-king") || (f == "--king-cutoff") || (f == "--king-cutoff-table") || (f == "--king-table-subset") || (f == "--king-table-require") ||
+      (f == "--king-table-require-xor")) {
+    die(63, "Error: %s is not supported by plink2-hip (--make-king-table and --king-table-filter are).\n", f.c_str());
+  }
   if (f == "--bad-freqs") {
     A.bad_freqs = true;
     return true;
@@ -988,7 +1047,16 @@ void check_flag_combinations(Args& A) {
   } else if (A.clump_unphased) {
     die(8, "Error: --clump-unphased must be used with --clump.\n");
   }
-  if (!A.have_prune && !A.have_r2 && !A.any_report() && !A.het && !A.hardy) {
+  if (A.king_filter_given && !A.king) {
+    die(8, "Error: --king-table-filter must be used with --make-king-table.\n");
+  }
+  if (A.king_filter_given && !(A.king_cols & kKingColId)) {  // plink2.cc:8563-8566
+    die(8, "Error: --king-table-filter requires --make-king-table cols= to include the 'id'\ncolumn set.\n");
+  }
+  if (A.king && (A.parallel_tot != 1)) {
+    die(63, "Error: --parallel with --make-king-table is not supported by plink2-hip.\n");
+  }
+  if (!A.have_prune && !A.have_r2 && !A.any_report() && !A.het && !A.hardy && !A.king) {
     die(8, "Error: no command given (plink2-hip implements --indep-pairwise and --r2-unphased matrices).\n");
   }
   if (A.have_prune && (A.parallel_tot != 1)) {

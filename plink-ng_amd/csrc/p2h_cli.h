@@ -225,6 +225,11 @@ struct Args {
   bool hwe = false, hwe_midp = false, hwe_keep_fewhet = false;
   double hwe_ln_thresh = 0.0, hwe_sample_size_term = -1.0;
   bool hardy = false, hardy_zs = false, hardy_midp = false;
+  // --make-king-table ['zs'] ['counts'] ['cols='...] and --king-table-filter <x> (p2h_king.cpp): the KING-robust table over every pair of kept
+  // samples, after every filter -- a command of its own or beside any other
+  bool king = false, king_zs = false, king_counts = false, king_cols_given = false, king_filter_given = false;
+  uint32_t king_cols = 0;                // kKingCol*
+  double king_filter = -DBL_MAX;         // lines with kinship < this are left out
   bool bad_freqs = false;  // --bad-freqs: --het may estimate allele frequencies from fewer than 50 founders (plink2.cc:2076)
   bool timing = false;    // --timing: print per-phase wall times
   bool dry_run = false;  // parse + plan only, print the parameters exactly (%a) and exit: used by the CPU tests
@@ -249,6 +254,13 @@ enum : uint32_t {
   kClumpColSp2 = 1u << 15,
   kClumpColDefault = kClumpColChrom | kClumpColPos | kClumpColMaybeprovref | kClumpColMaybeA1 | kClumpColMaybeF | kClumpColTotal | kClumpColMaybeBounds |
                      kClumpColBins | kClumpColSp2
+};
+
+// --make-king-table cols= (plink2_matrix_calc.h: kfKingCol*)
+enum : uint32_t {
+  kKingColMaybefid = 1u << 0, kKingColFid = 1u << 1, kKingColId = 1u << 2, kKingColMaybesid = 1u << 3, kKingColSid = 1u << 4, kKingColNsnp = 1u << 5,
+  kKingColHethet = 1u << 6, kKingColIbs0 = 1u << 7, kKingColIbs1 = 1u << 8, kKingColIbs = 1u << 9, kKingColKinship = 1u << 10,
+  kKingColDefault = kKingColMaybefid | kKingColId | kKingColMaybesid | kKingColNsnp | kKingColHethet | kKingColIbs0 | kKingColKinship
 };
 
 // test / measurement hooks of the front-end (hidden --debug-* flags; the library itself reads no environment, csrc/ldp_env.h)
@@ -579,6 +591,9 @@ struct Session {
   bool het_device = false;
   const char* het_host_reason = nullptr;
   std::vector<uint32_t> report_variants;
+  // --make-king-table: the pair counts from the resident image after the filters (king_device: the conditions of het_device), or king_host_pass()
+  bool king_device = false;
+  const char* king_host_reason = nullptr;
   // --hwe / --hardy on the host's pass: seconds spent in ldp_hwe_ln_p_host on the reader's threads, p-values computed, tolerance ties among them
   double hwe_host_s = 0.0;
   uint32_t hwe_host_ct = 0, hwe_host_ties = 0;
@@ -710,6 +725,38 @@ void het_write(const Session& S, const HetPlan& plan, const HetSums& sums);
 void het_preamble(const Session& S, uint32_t autosomal, uint32_t non_autosomal);
 // the host's pass: the autosomal variants of the final list (S.inc), every kept sample; p2h_inputs.cpp, beside the other passes over the rows
 void het_host_pass(Session& S);
+
+// ---- --make-king-table (p2h_king.cpp): the KING-robust table, CalcKing (plink2_matrix_calc.cc:1662-2460) ----
+// The one writer both sources of the counts go through: the device's (run_prune: ldp_king_counts_block / ldp_king_block_hits) and the host's
+// pass (king_host_pass).  Lines come row ascending, column ascending; row and col index the kept samples in file order, the line's first
+// sample being the later one.
+class KingWriter {
+ public:
+  explicit KingWriter(const Session& S);
+  // one pair: the kinship is formed here from the integers (ComputeKinship), the filter applied, the line appended
+  void pair(uint32_t row, uint32_t col, const ldp_king_counts_t& c);
+  // pairs the device's hit form left out: they count as filtered
+  void add_filtered(uint64_t n) { filtered_ += n; }
+  // closes the file, writes <out>.kin0.id where 'id' is not among the columns, and logs what the reference logs; variant_ct: variants processed
+  void finish(uint32_t variant_ct);
+
+ private:
+  const Session& S_;
+  std::vector<uint32_t> kept_;  // sample of the file per kept sample
+  std::vector<std::string> ids_;  // the ID columns of every kept sample, tab-terminated
+  bool col_fid_ = false, col_sid_ = false;
+  OutFile f_;
+  std::string path_, buf_;
+  uint64_t filtered_ = 0, pairs_ = 0;
+};
+// the log lines and errors CalcKing has before it reads a genotype (fewer than two samples; non-autosomal variants excluded, none left)
+void king_preamble(const Session& S, uint32_t sample_ct, uint32_t autosomal, uint32_t non_autosomal);
+// The host's popcount pass over sample-major bit-planes (words per sample: het, hom, hom-ALT over the variants): every pair in the table's order
+// through the writer, on `nthreads` threads
+void king_pairs_host(const std::vector<uint64_t>& het, const std::vector<uint64_t>& hom, const std::vector<uint64_t>& alt, size_t words, uint32_t sample_ct, uint32_t nthreads,
+                     KingWriter* w);
+// the host's pass: main-track rows of the autosomal variants of the final list (S.inc), every kept sample; p2h_inputs.cpp, beside the other passes over the rows
+void king_host_pass(Session& S);
 void logprintf_ww(const char* fmt, ...);  // logprintf with the reference's word wrap at 79 columns (logprintfww)
 
 void load_inputs(Session& S, int argc, char** argv);

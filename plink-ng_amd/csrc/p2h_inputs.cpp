@@ -228,7 +228,7 @@ CountFilters::CountFilters(const Args& args, uint32_t kept_samples) : A(args) {
   min_maf = A.min_maf * (1.0 - kSmallEpsilon);
   max_maf = A.max_maf * (1.0 + kSmallEpsilon);
   // (a run of --hardy alone: the reference applies --geno, which the report depends on, and none of the filters behind the report)
-  const bool consumer = A.have_prune || A.have_r2 || A.het;
+  const bool consumer = A.have_prune || A.have_r2 || A.het || A.king;
   freq_on = freq_on && consumer;
   hwe_on = A.hwe && consumer;
   hwe_ln_base = A.hwe_ln_thresh * (1 + kSmallEpsilon);
@@ -310,7 +310,7 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
   if (g_dbg.host_filter) {
     return "--debug-host-filter";
   }
-  if (((!A.have_prune) && (A.have_r2 || !(A.any_report() || A.het || A.hardy))) || A.pairphase) {  // (a run of reports, of --het or of --hardy alone loads like the prune)
+  if (((!A.have_prune) && (A.have_r2 || !(A.any_report() || A.het || A.hardy || A.king))) || A.pairphase) {  // (a run of reports, of --het, of --hardy or of --make-king-table alone loads like the prune)
     return A.pairphase ? "--indep-pairphase plans its engines before the load" : "the r^2 outputs and --clump plan their engines before the load";
   }
   if (A.gpus != 1) {
@@ -804,6 +804,126 @@ void het_host_pass(Session& S) {
   }
 }
 
+// The --make-king-table stage of load_inputs(), het_stage's neighbour: where the pair counts come from -- the resident image after the filters
+// (S.king_device: the conditions of het_device), or king_host_pass().  The table is made of hardcalls, so a dosage file is no refusal: it
+// takes the host's pass.
+static void king_stage(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
+  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chromosome 0, 3 = chrX / chrY / MT
+  bool any_non_autosomal = false, any_multiallelic = false;
+  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
+    auto it = chr_state.find(V.chrom[v]);
+    if (it == chr_state.end()) {
+      const std::string& cur = V.chrom[v];
+      const int code = chrom_code(cur);
+      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
+                                       (A.autosome && !((code >= 1) && (code <= 22))));
+      bool zero = false;
+      const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
+      it = chr_state.emplace(cur, static_cast<uint8_t>(out ? 1 : (zero ? 2 : ((cls >= 3) ? 3 : 0)))).first;
+    }
+    if ((it->second == 1) || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
+      continue;
+    }
+    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
+      continue;
+    }
+    if ((it->second == 2) && (A.have_prune || (A.r2_table && !A.r2_inter))) {
+      // (the reference's table counts unplaced variants as autosomal; the prune and the windowed tables strip them from the one list kept here)
+      die(63, "Error: --make-king-table beside %s with chromosome 0 variants ('%s') is not supported by plink2-hip: run it on its own, or filter them out (--not-chr 0).\n",
+          A.have_prune ? "the prune" : "a windowed r^2 command", V.id[v].c_str());
+    }
+    any_non_autosomal = any_non_autosomal || (it->second == 3);
+    any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
+  }
+  uint32_t kept_samples = 0, founders = 0;
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    kept_samples += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
+    founders += S.is_founder[sx];
+  }
+  const char* reason = device_filter_refusal(A, false, founders, founders);
+  if (!reason) {
+    reason = (kept_samples != founders) ? "non-founders among the kept samples (the table lists them, the device's rows hold founders only)"
+             : (ldp_pgen_has_dosage(S.pg) ? "the file has dosage tracks" : nullptr);
+  }
+  if (!reason) {
+    reason = (founders < 2) ? "fewer than two founders (no engine)"
+             : ((founders > ldp_matrix_pipe_max_founders()) ? "more founders than the resident 2-bit image takes (the pair counts are read off it)"
+             : (any_non_autosomal ? "chrX / chrY / MT variants (their rows are built for engines of their own)"
+             : (any_multiallelic ? "multiallelic variants (their rows are collapsed on the way into the image)" : nullptr)));
+  }
+  if (A.dry_run) {
+    char num[40];
+    *format_g6(A.king_filter, num) = '\0';
+    logprintf("dry-run: --make-king-table: cols 0x%x%s%s, filter %s; %s%s\n", A.king_cols, A.king_counts ? ", counts" : "", A.king_zs ? ", zs" : "", A.king_filter_given ? num : "none",
+              reason ? "host pass: " : "from the resident image", reason ? reason : "");
+  }
+  S.king_device = (!reason) && !A.dry_run;  // (a dry run prints the decision and touches no device)
+  S.king_host_reason = reason ? reason : "--dry-run";
+}
+
+void king_host_pass(Session& S) {
+  const Args& A = S.A;
+  const double t0 = now_s();
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  std::vector<uint32_t> todo;  // the autosomal variants of the final list (chromosome 0 counts as one, CountNonAutosomalVariants plink2_common.cc:3334)
+  uint32_t non_autosomal = 0;
+  for (size_t k = 0; k < S.inc.size(); ++k) {
+    if (S.vcls[k] >= 3) {
+      ++non_autosomal;
+    } else {
+      todo.push_back(S.inc[k]);
+    }
+  }
+  std::vector<uint32_t> kept;  // sample of the file per kept sample
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    if (S.sample_kept.empty() || S.sample_kept[sx]) {
+      kept.push_back(sx);
+    }
+  }
+  const uint32_t sample_ct = static_cast<uint32_t>(kept.size());
+  king_preamble(S, sample_ct, static_cast<uint32_t>(todo.size()), non_autosomal);
+  // sample-major bit-planes over the variants of the list: het, hom, hom-ALT (.bed: hom-A1).  Two threads may hold variants of the same word.
+  const size_t words = (todo.size() + 63) / 64;
+  std::vector<uint64_t> het(static_cast<size_t>(sample_ct) * words, 0), hom(het.size(), 0), alt(het.size(), 0);
+  const bool bed = (S.storage_mode == 0x01);
+  const uint64_t rec_bytes = S.rec_bytes;
+  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  for_each_row_run(S.pg, S.gpath, S.direct_rows, rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
+    for (uint32_t r = 0; r < n; ++r) {
+      const uint8_t* row = rows + static_cast<uint64_t>(r) * rec_bytes;
+      const size_t w = (q + r) >> 6;
+      const uint64_t bit = 1ull << ((q + r) & 63);
+      for (uint32_t s = 0; s < sample_ct; ++s) {
+        const uint32_t c = code_at(row, kept[s]);
+        // .pgen: 00 hom-REF, 01 het, 10 hom-ALT, 11 missing; .bed: 00 hom-A1, 01 missing, 10 het, 11 hom-A2 (pgenlib_read.cc:2157)
+        const bool is_het = bed ? (c == 2) : (c == 1);
+        const bool is_hom = bed ? ((c == 0) || (c == 3)) : ((c == 0) || (c == 2));
+        const bool is_alt = bed ? (c == 0) : (c == 2);
+        if (is_het) {
+          __atomic_fetch_or(&het[static_cast<size_t>(s) * words + w], bit, __ATOMIC_RELAXED);
+        } else if (is_hom) {
+          __atomic_fetch_or(&hom[static_cast<size_t>(s) * words + w], bit, __ATOMIC_RELAXED);
+          if (is_alt) {
+            __atomic_fetch_or(&alt[static_cast<size_t>(s) * words + w], bit, __ATOMIC_RELAXED);
+          }
+        }
+      }
+    }
+  });
+  const double t1 = now_s();
+  KingWriter w(S);
+  king_pairs_host(het, hom, alt, words, sample_ct, nthreads, &w);
+  w.finish(static_cast<uint32_t>(todo.size()));
+  if (A.timing) {
+    logprintf("[timing] --make-king-table: host pass (%u samples, %zu variants; bit-planes %.3f s, pairs and writing %.3f s; %s)\n", sample_ct, todo.size(), t1 - t0, now_s() - t1,
+              S.king_host_reason ? S.king_host_reason : "the r^2 outputs and --clump plan their engines before the load");
+  }
+}
+
 void load_inputs(Session& S, int argc, char** argv) {
   S.t_begin = S.t_begin_first ? S.t_begin_first : now_s();
   S.A = parse_args(argc, argv);
@@ -835,7 +955,7 @@ void load_inputs(Session& S, int argc, char** argv) {
   const bool sample_filter = (!A.keep_files.empty()) || (!A.remove_files.empty());
   const bool mind_on = (A.mind < 1.0);  // plink2.cc:8910
   std::vector<std::pair<std::string, std::string>> parent_keys;
-  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on || A.rep_smiss() || A.het) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
+  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on || A.rep_smiss() || A.het || A.king) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
                &S.sample_sids);
   // --make-founders (MakeFounders, plink2_filter.cc:4372-4443): a non-founder with a parent (both, with 'require-2-missing') that
   // is not among the samples in play becomes a founder; 'first' applies it before --keep / --remove, else after them
@@ -1037,8 +1157,11 @@ void load_inputs(Session& S, int argc, char** argv) {
   if (A.het) {
     het_stage(S, chr_filter, extract_ids, exclude_ids);
   }
+  if (A.king) {
+    king_stage(S, chr_filter, extract_ids, exclude_ids);
+  }
   const bool hwe_any = A.hwe || A.hardy;
-  if ((freq_filter || (A.geno != 1.0) || hwe_any) && (A.have_prune || A.have_r2 || A.het || A.hardy)) {
+  if ((freq_filter || (A.geno != 1.0) || hwe_any) && (A.have_prune || A.have_r2 || A.het || A.hardy || A.king)) {
     std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chrX, 4 = chrY / MT (--hwe / --hardy alone: neither tested nor listed)
     std::vector<uint32_t> todo;
     std::vector<uint8_t> todo_haploid;
@@ -1203,6 +1326,10 @@ void load_inputs(Session& S, int argc, char** argv) {
     S.device_filter = true;
     S.kept_sample_ct = founder_ct;
   }
+  if (S.king_device && !S.device_filter) {  // (... and --make-king-table)
+    S.device_filter = true;
+    S.kept_sample_ct = founder_ct;
+  }
   {
     std::unordered_set<std::string> seen_chr;
     std::string cur;
@@ -1343,6 +1470,9 @@ void load_inputs(Session& S, int argc, char** argv) {
     // (the r^2 outputs and --clump keep the host's filters: the variant list is final here.  Beside the prune, or alone, run_prune() calls the
     // pass once its list is -- after the device's filters, after a --mind decided there)
     het_host_pass(S);
+  }
+  if (A.king && A.have_r2 && !A.dry_run) {
+    king_host_pass(S);
   }
 }
 

@@ -951,6 +951,95 @@ struct PruneJob {
     }
   }
 
+  // --make-king-table from the resident image (Session::king_device; the conditions of het_on_device: row q is variant q of the list, column f
+  // founder f of the file = kept sample f).  Row blocks of samples against every earlier sample, sized so that a block holds at most 2^24 pairs
+  // (the library keeps 20 bytes per pair of the block on the device): the dense form without --king-table-filter, the hit form with it -- the
+  // device drops the pairs below the threshold, the writer forms the doubles it prints from the returned integers again -- and either way the
+  // lines leave in the table's order, row ascending, column ascending.
+  void king_on_device() {
+    const double t0 = now_s();
+    if (m_ct != variant_ct) {
+      die(16, "\nError: internal: --make-king-table lists %u variants and %u rows are loaded.\n", variant_ct, m_ct);
+    }
+    king_preamble(S, founder_ct, m_ct, 0);
+    KingWriter w(S);
+    const uint64_t kBlockPairs = 1ull << 24;
+    std::vector<ldp_king_counts_t> dense;
+    std::vector<ldp_king_hit> hits;
+    double ms_total = 0.0, call_s = 0.0;
+    uint64_t pair_variants = 0;
+    uint32_t blocks = 0;
+    for (uint32_t r0 = 1; r0 < founder_ct;) {
+      // rows [r0, r1) against columns [0, r1 - 1)
+      uint32_t rows = static_cast<uint32_t>(std::min<uint64_t>(4096, std::max<uint64_t>(32, kBlockPairs / (static_cast<uint64_t>(r0) + 32))));
+      rows = std::min(rows, founder_ct - r0);
+      while ((rows > 32) && (static_cast<uint64_t>(rows) * (r0 + rows - 1) > kBlockPairs)) {
+        rows = std::max(32u, rows / 2);
+      }
+      const uint32_t r1 = r0 + rows, cols = r1 - 1;
+      const uint64_t block_pairs = (static_cast<uint64_t>(r1) * (r1 - 1) - static_cast<uint64_t>(r0) * (r0 - 1)) / 2;
+      const double tc = now_s();
+      if (A.king_filter_given) {
+        if (hits.empty()) {
+          hits.resize(1u << 20);
+        }
+        uint64_t found = 0;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+          if (ldp_king_block_hits(eng[0], 0, m_ct, nullptr, r0, rows, 0, cols, A.king_filter, hits.data(), hits.size(), &found)) {
+            die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+          }
+          if (found <= hits.size()) {
+            break;
+          }
+          hits.resize(found);  // (more pairs pass than the list held: once more with room for all of them)
+        }
+        call_s += now_s() - tc;
+        std::sort(hits.begin(), hits.begin() + found, [](const ldp_king_hit& a, const ldp_king_hit& b) { return (a.row != b.row) ? (a.row < b.row) : (a.col < b.col); });
+        for (uint64_t k = 0; k < found; ++k) {
+          w.pair(hits[k].row, hits[k].col, hits[k].c);
+        }
+        w.add_filtered(block_pairs - found);
+        pair_variants += block_pairs * m_ct;
+      } else {
+        dense.resize(static_cast<size_t>(rows) * cols);
+        double ms = 0.0;
+        uint64_t pv = 0;
+        if (ldp_debug_king_counts_block(eng[0], 0, m_ct, nullptr, r0, rows, 0, cols, dense.data(), cols, 0, &ms, &pv)) {
+          die(16, "\nError: %s\n", ldp_last_error(eng[0]));
+        }
+        call_s += now_s() - tc;
+        ms_total += ms;
+        pair_variants += pv;
+        for (uint32_t i = r0; i < r1; ++i) {
+          const ldp_king_counts_t* row = dense.data() + static_cast<size_t>(i - r0) * cols;
+          for (uint32_t j = 0; j < i; ++j) {
+            w.pair(i, j, row[j]);
+          }
+        }
+      }
+      ++blocks;
+      r0 = r1;
+    }
+    w.finish(m_ct);
+    if (A.timing) {
+      const double total = now_s() - t0;
+      if (A.king_filter_given) {
+        logprintf("[timing] --make-king-table: from the resident image (%u samples, %u rows, %u blocks, hit form; the calls %.3f s = %.3g pair-variants/s; sorting and writing %.3f s)\n",
+                  founder_ct, m_ct, blocks, call_s, (call_s > 0.0) ? (static_cast<double>(pair_variants) / call_s) : 0.0, total - call_s);
+      } else {
+        logprintf("[timing] --make-king-table: from the resident image (%u samples, %u rows, %u blocks, dense form; kernels %.3f ms = %.3g pair-variants/s; the calls %.3f s, writing %.3f s)\n",
+                  founder_ct, m_ct, blocks, ms_total, (ms_total > 0.0) ? (static_cast<double>(pair_variants) / (ms_total * 1e-3)) : 0.0, call_s, total - call_s);
+      }
+    }
+  }
+  void king_stage() {
+    if (S.king_device) {
+      king_on_device();
+    } else {
+      king_host_pass(S);
+    }
+  }
+
   // --geno / --maf / --max-maf / --mac / --max-mac from the records the load's own count pass left on the device (nm_ct and the three
   // genotype counts of every row, over the founders = the kept samples: device_filter_refusal): the arithmetic of the host's pass
   // (CountFilters), then the engine drops the variants that go and plans over the rest (ldp_restrict_variants), and the session's variant
@@ -1405,11 +1494,14 @@ struct PruneJob {
   }
 
   int run() {
-    if ((!A.have_prune) && (!S.report_device) && !((A.het || A.hardy) && S.device_filter)) {
+    if ((!A.have_prune) && (!S.report_device) && !((A.het || A.hardy || A.king) && S.device_filter)) {
       if (A.het) {
         het_host_pass(S);  // (the host's filters made the list final in load_inputs)
       }
-      finish();  // a run of reports or of --het alone that the host's passes served: no device is touched
+      if (A.king && !A.dry_run) {
+        king_host_pass(S);
+      }
+      finish();  // a run of reports, of --het or of --make-king-table alone that the host's passes served: no device is touched
     }
     set_params();
     if (A.dry_run) {
@@ -1438,7 +1530,7 @@ struct PruneJob {
       }
       if (S.report_device) {
         reports_on_device();
-        if ((!A.have_prune) && (!A.het) && !A.hardy) {
+        if ((!A.have_prune) && (!A.het) && (!A.hardy) && !A.king) {
           S.file_to_hbm_done();
           finish();  // a run of reports alone stops here: no plan, no pair kernel
         }
@@ -1450,6 +1542,9 @@ struct PruneJob {
         report_filter_timing();
         if (A.het) {
           het_stage();  // --het alone, after the filters: no band plan, no pair kernel
+        }
+        if (A.king) {
+          king_stage();  // (the same for --make-king-table, behind --het)
         }
         S.file_to_hbm_done();
         finish();
@@ -1495,6 +1590,9 @@ struct PruneJob {
     write_lists();
     if (A.het) {
       het_stage();  // (right behind LdPrune, plink2.cc:2958; the restricted engine's image is as the filters left it)
+    }
+    if (A.king) {
+      king_stage();
     }
     finish();
   }
