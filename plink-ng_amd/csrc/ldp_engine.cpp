@@ -41,6 +41,58 @@ int hipfail(ldp_engine* e, hipError_t rc, const char* what) {
   return fail(e, LDP_ERR_GPU, std::string(what) + ": " + hipGetErrorString(rc));
 }
 
+// The contract of the passes over resident rows: a planned engine answers for the variants [first_variant, first_variant + n)
+// as it is -- before or after ldp_restrict_variants(), nothing of it changes -- when it is not sharded, its rows are plain hardcalls, it owns a
+// row for every variant of the range and every such row is loaded; needs_image: the pass reads the 2-bit code image, which a bit-plane engine
+// does not have.  *runs: the range as the runs of consecutive rows the engine owns it in (one launch each).  who: the public name of the call,
+// for the messages.  The checks stay in this order: a call that is wrong in one way gets that way's code and text.
+int resident_runs(ldp_engine* e, const char* who, uint32_t first_variant, uint32_t n, bool needs_image, std::vector<ResidentRun>* runs) {
+  const std::string name(who);
+  if (static_cast<uint64_t>(first_variant) + n > e->variant_ct) {
+    return fail(e, LDP_ERR_INVALID, "variant range out of bounds");
+  }
+  if (e->world > 1) {
+    return fail(e, LDP_ERR_UNSUPPORTED, name + " on a sharded engine (ldp_set_shard with world > 1)");
+  }
+  if (needs_image && ((e->P.founder_ct > kMfMaxFounders) || !e->opt.pair_mfma || (e->plan_uploaded && !e->codes_format))) {
+    return fail(e, LDP_ERR_UNSUPPORTED, name + " on an engine that keeps bit-planes (no 2-bit code image)");
+  }
+  if (e->loaded_special) {
+    return fail(e, LDP_ERR_UNSUPPORTED, name + " on rows loaded as LDP_GENO_PHASED or through a sample map that makes het calls missing");
+  }
+  const uint32_t end = first_variant + n;
+  runs->clear();
+  uint32_t covered = 0;
+  for (const ldp_engine::OwnedRun& r : e->owned_runs) {
+    const uint32_t a = std::max(r.g_first, first_variant), b = std::min(r.g_end, end);
+    if (a < b) {
+      runs->push_back({static_cast<uint32_t>(e->global_to_local[a]), b - a, a - first_variant});
+      covered += b - a;
+    }
+  }
+  if (covered != n) {
+    return fail(e, LDP_ERR_STATE, "a variant of the range has no row in this engine (its plan did not own it)");
+  }
+  if (n && !e->plan_uploaded) {
+    return fail(e, LDP_ERR_STATE, "nothing is loaded");
+  }
+  for (const ResidentRun& r : *runs) {
+    for (uint32_t l = r.l_first; l < r.l_first + r.ct; ++l) {
+      if (!e->loaded[l]) {
+        return fail(e, LDP_ERR_STATE, "genotypes missing for a variant of the range (ldp_load_genotypes)");
+      }
+    }
+  }
+  return LDP_OK;
+}
+
+int begin_resident_read(ldp_engine* e) {
+  HIP_TRY(e, hipSetDevice(e->device));
+  // the count pass of the loads (it writes each row's padding, inverts ALT-major rows and fills the records) is finished before rows or records are read
+  HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+  return LDP_OK;
+}
+
 void free_device(ldp_engine* e, bool keep_image) {
   if (!e->gpu_ok) {
     return;

@@ -1,8 +1,8 @@
 // ldp_engine_hwe.cpp -- ldp_hwe_ln_pvals(): the exact Hardy-Weinberg test of loaded rows, from the genotype counts the count pass left in the
 // records on the device (hwe_kernel, ldp_hwe.hip), and ldp_hwe_ln_pvals_counts(), the same kernel on counts from
-// anywhere.  States and refusals of the engine call are those of ldp_sample_het_counts() -- nothing of the engine changes, before as after
-// ldp_restrict_variants(), the requested variants walked as the runs of consecutive rows the engine owns them in (one launch per run) --
-// except that the image is not read: engines that keep bit-planes are served too, and a row whose record carries no raw counts is refused.
+// anywhere.  Contract, states and refusals of the engine call are those of resident_runs() (ldp_engine.cpp; one launch per run of owned
+// records), with three deviations marked below: the image is not read, so engines that keep bit-planes are served too; the records have to
+// be on the device; and a row whose record carries no raw counts (loaded as LDP_GENO_INVERSE) is refused.
 // (host runtime behind include/ldprune_hip.h; ldp_engine.cpp has the overview)
 #include "ldp_engine_internal.h"
 
@@ -21,39 +21,19 @@ int hwe_ln_pvals_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, int mid
   if (!ln_p) {
     return fail(e, LDP_ERR_INVALID, "ln_p is NULL");
   }
-  if (static_cast<uint64_t>(first_variant) + n > e->variant_ct) {
-    return fail(e, LDP_ERR_INVALID, "variant range out of bounds");
+  // HWE's own: the records are read, not the image, so an engine that keeps bit-planes is served (no needs_image)
+  std::vector<ResidentRun> runs;
+  int rc = resident_runs(e, "ldp_hwe_ln_pvals()", first_variant, n, false, &runs);
+  if (rc) {
+    return rc;
   }
-  if (e->world > 1) {
-    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_hwe_ln_pvals() on a sharded engine (ldp_set_shard with world > 1)");
-  }
-  if (e->loaded_special) {
-    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_hwe_ln_pvals() on rows loaded as LDP_GENO_PHASED or through a sample map that makes het calls missing");
-  }
-  const uint32_t end = first_variant + n;
-  struct Run {
-    uint32_t l_first, ct, off;  // record, records, first variant's offset in the range
-  };
-  std::vector<Run> runs;
-  uint32_t covered = 0;
-  for (const ldp_engine::OwnedRun& r : e->owned_runs) {
-    const uint32_t a = std::max(r.g_first, first_variant), b = std::min(r.g_end, end);
-    if (a < b) {
-      runs.push_back({static_cast<uint32_t>(e->global_to_local[a]), b - a, a - first_variant});
-      covered += b - a;
-    }
-  }
-  if (covered != n) {
-    return fail(e, LDP_ERR_STATE, "a variant of the range has no row in this engine (its plan did not own it)");
-  }
-  if (n && (!e->plan_uploaded || !e->d_recs)) {
+  // HWE's own: what is read are the records of the device-side plan
+  if (n && !e->d_recs) {
     return fail(e, LDP_ERR_STATE, "nothing is loaded");
   }
-  for (const Run& r : runs) {
+  // HWE's own: the record of a row that came inverted holds no raw genotype counts
+  for (const ResidentRun& r : runs) {
     for (uint32_t l = r.l_first; l < r.l_first + r.ct; ++l) {
-      if (!e->loaded[l]) {
-        return fail(e, LDP_ERR_STATE, "genotypes missing for a variant of the range (ldp_load_genotypes)");
-      }
       if (e->row_inv_loaded[l]) {
         return fail(e, LDP_ERR_UNSUPPORTED, "ldp_hwe_ln_pvals() on a row loaded as LDP_GENO_INVERSE (its record carries no genotype counts)");
       }
@@ -62,9 +42,10 @@ int hwe_ln_pvals_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, int mid
   if (!n) {
     return LDP_OK;
   }
-  HIP_TRY(e, hipSetDevice(e->device));
-  // the count pass of the loads writes the records on this stream's behalf: it is finished before they are read
-  HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+  rc = begin_resident_read(e);
+  if (rc) {
+    return rc;
+  }
   // one allocation: ln_p (64-bit) | flags (bytes)
   const size_t off_flags = static_cast<size_t>(n) * 8;
   DevBuf d_all;
@@ -74,7 +55,7 @@ int hwe_ln_pvals_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, int mid
   double* d_ln = d_all.as<double>();
   uint8_t* d_flags = d_all.as<uint8_t>() + off_flags;
   HIP_TRY(e, hipEventRecord(ev.ev[0], e->stream));
-  for (const Run& r : runs) {
+  for (const ResidentRun& r : runs) {
     const hipError_t krc = launch_hwe(e->d_recs + r.l_first, nullptr, nullptr, nullptr, r.ct, midp ? 1 : 0, d_ln + r.off, d_flags + r.off, e->stream);
     if (krc != hipSuccess) {
       return hipfail(e, krc, "hwe_kernel launch");
@@ -86,13 +67,8 @@ int hwe_ln_pvals_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, int mid
     HIP_TRY(e, hipMemcpyAsync(flags, d_flags, n, hipMemcpyDeviceToHost, e->stream));
   }
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
   if (ms_kernel) {
-    *ms_kernel = ms;
+    *ms_kernel = ev.elapsed_ms(0, 1);
   }
   return LDP_OK;
 }
@@ -159,13 +135,8 @@ int hwe_ln_pvals_counts_impl(int device, uint32_t n, const uint32_t* hom1, const
   }
   HWE_TRY(hipStreamSynchronize(st.s));
 #undef HWE_TRY
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
   if (ms_kernel) {
-    *ms_kernel = ms;
+    *ms_kernel = ev.elapsed_ms(0, 1);
   }
   return LDP_OK;
 }

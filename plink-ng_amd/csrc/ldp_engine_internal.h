@@ -465,6 +465,15 @@ struct EventSet {
     }
     return hipSuccess;
   }
+  // device time from event a to event b; 0 where it cannot be read (a time that is reported, never the call's result)
+  float elapsed_ms(int a, int b) const {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) {
+      (void)hipGetLastError();
+      ms = 0.f;
+    }
+    return ms;
+  }
 };
 
 // temporary device allocation released on every exit path
@@ -496,6 +505,12 @@ int ensure_device_plan(ldp_engine* e);
 int ensure_staging(ldp_engine* e);
 int start_fetch_recs(ldp_engine* e);
 int fetch_recs(ldp_engine* e);
+// ldp_engine.cpp: the frame of the passes over resident rows (ldp_sample_missing_counts, ldp_sample_het_counts, ldp_king_*, ldp_hwe_ln_pvals)
+struct ResidentRun {
+  uint32_t l_first, ct, off;  // image row (= record), rows, first variant's offset in the caller's range
+};
+int resident_runs(ldp_engine* e, const char* who, uint32_t first_variant, uint32_t n, bool needs_image, std::vector<ResidentRun>* runs);
+int begin_resident_read(ldp_engine* e);
 // ldp_engine_run.cpp: launches and replay
 void replay(ldp_engine* e, const uint32_t* pred, const double* mf, std::vector<uint32_t>& R, uint64_t* replay_pairs_out);
 int finish_removed(ldp_engine* e, const std::vector<uint32_t>& R, uint64_t* removed);

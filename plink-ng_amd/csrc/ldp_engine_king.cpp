@@ -1,8 +1,8 @@
 // ldp_engine_king.cpp -- ldp_king_counts_block() / ldp_king_block_hits(): the KING-robust counts of the sample pairs of a block, from the
-// resident 2-bit image (ldp_king.hip).  Contract, states and refusals are those of ldp_sample_het_counts(): nothing of
-// the engine changes, before as after ldp_restrict_variants(), and the requested variants are walked as the runs of consecutive image rows the
-// engine owns them in.  Each run is cut into slabs; per slab the row samples' and the column samples' strips are written (one set when both
-// ranges start in the same group of samples and the rows reach at least as far) and one pair launch adds the slab's counts to the block's.
+// resident 2-bit image (ldp_king.hip).  Contract, states and refusals are those of resident_runs() (ldp_engine.cpp),
+// with the image, behind the call's own argument checks (the debug form answers under the public call's name).  Each run of owned rows is
+// cut into slabs; per slab the row samples' and the column samples' strips are written (one set when both ranges start in the same group of
+// samples and the rows reach at least as far) and one pair launch adds the slab's counts to the block's.
 // (host runtime behind include/ldprune_hip.h; ldp_engine.cpp has the overview)
 #include "ldp_engine_internal.h"
 #include "ldp_king_device.h"
@@ -32,7 +32,6 @@ int king_impl(ldp_engine* e, const char* who, const KingRequest& q, ldp_king_cou
   if (count) {
     *count = 0;
   }
-  const std::string name(who);
   if (!e->planned) {
     return fail(e, LDP_ERR_STATE, "ldp_set_variants*() and the loads first");
   }
@@ -45,9 +44,6 @@ int king_impl(ldp_engine* e, const char* who, const KingRequest& q, ldp_king_cou
   } else if (ld_elems < q.col_ct) {
     return fail(e, LDP_ERR_INVALID, "ld_elems is smaller than col_ct");
   }
-  if (static_cast<uint64_t>(q.first_variant) + q.n > e->variant_ct) {
-    return fail(e, LDP_ERR_INVALID, "variant range out of bounds");
-  }
   const uint32_t founder_ct = e->P.founder_ct;
   if ((static_cast<uint64_t>(q.row_first) + q.row_ct > founder_ct) || (static_cast<uint64_t>(q.col_first) + q.col_ct > founder_ct)) {
     return fail(e, LDP_ERR_INVALID, "sample range beyond founder_ct");
@@ -55,40 +51,10 @@ int king_impl(ldp_engine* e, const char* who, const KingRequest& q, ldp_king_cou
   if (slab_variants && ((slab_variants % ldp::kKingSlabMin) || (slab_variants > ldp::kKingSlabMax))) {
     return fail(e, LDP_ERR_INVALID, "slab_variants: a multiple of 256, at most 65536");
   }
-  if (e->world > 1) {
-    return fail(e, LDP_ERR_UNSUPPORTED, name + " on a sharded engine (ldp_set_shard with world > 1)");
-  }
-  if ((founder_ct > kMfMaxFounders) || !e->opt.pair_mfma || (e->plan_uploaded && !e->codes_format)) {
-    return fail(e, LDP_ERR_UNSUPPORTED, name + " on an engine that keeps bit-planes (no 2-bit code image)");
-  }
-  if (e->loaded_special) {
-    return fail(e, LDP_ERR_UNSUPPORTED, name + " on rows loaded as LDP_GENO_PHASED or through a sample map that makes het calls missing");
-  }
-  const uint32_t end = q.first_variant + q.n;
-  struct Run {
-    uint32_t l_first, ct, off;  // image row, rows, first variant's offset in the range
-  };
-  std::vector<Run> runs;
-  uint32_t covered = 0;
-  for (const ldp_engine::OwnedRun& r : e->owned_runs) {
-    const uint32_t a = std::max(r.g_first, q.first_variant), b = std::min(r.g_end, end);
-    if (a < b) {
-      runs.push_back({static_cast<uint32_t>(e->global_to_local[a]), b - a, a - q.first_variant});
-      covered += b - a;
-    }
-  }
-  if (covered != q.n) {
-    return fail(e, LDP_ERR_STATE, "a variant of the range has no row in this engine (its plan did not own it)");
-  }
-  if (q.n && !e->plan_uploaded) {
-    return fail(e, LDP_ERR_STATE, "nothing is loaded");
-  }
-  for (const Run& r : runs) {
-    for (uint32_t l = r.l_first; l < r.l_first + r.ct; ++l) {
-      if (!e->loaded[l]) {
-        return fail(e, LDP_ERR_STATE, "genotypes missing for a variant of the range (ldp_load_genotypes)");
-      }
-    }
+  std::vector<ResidentRun> runs;
+  int rc = resident_runs(e, who, q.first_variant, q.n, true, &runs);
+  if (rc) {
+    return rc;
   }
   if (dense) {
     for (uint32_t r = 0; r < q.row_ct; ++r) {
@@ -110,9 +76,10 @@ int king_impl(ldp_engine* e, const char* who, const KingRequest& q, ldp_king_cou
   if (!pairs) {
     return LDP_OK;  // (the hit form without a pair: no hit)
   }
-  HIP_TRY(e, hipSetDevice(e->device));
-  // the count pass of the loads (it writes each row's padding, and inverts ALT-major rows) is finished before the rows are read
-  HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+  rc = begin_resident_read(e);
+  if (rc) {
+    return rc;
+  }
   const uint32_t G = ldp::kKingStripSamples;
   const uint32_t row_end = q.row_first + q.row_ct, col_end = q.col_first + q.col_ct;
   const uint32_t a_base = q.row_first / G * G, b_base = q.col_first / G * G;
@@ -146,7 +113,7 @@ int king_impl(ldp_engine* e, const char* who, const KingRequest& q, ldp_king_cou
   uint8_t* strips_b = shared ? strips_a : strips_a + a_bytes;
   HIP_TRY(e, hipEventRecord(ev.ev[0], e->stream));
   if (work) {
-    for (const Run& r : runs) {
+    for (const ResidentRun& r : runs) {
       for (uint32_t s = 0; s < r.ct; s += K) {
         const uint32_t rows = std::min(K, r.ct - s);
         // (a short last slab runs its whole length only up to the next 256 variants: the rest would be code 11 against code 11)
@@ -191,13 +158,8 @@ int king_impl(ldp_engine* e, const char* who, const KingRequest& q, ldp_king_cou
                                 static_cast<size_t>(q.col_ct) * sizeof(ldp_king_counts_t), q.row_ct, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
   }
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
   if (ms_kernel) {
-    *ms_kernel = ms;
+    *ms_kernel = ev.elapsed_ms(0, 1);
   }
   if (pair_variants) {
     *pair_variants = pairs * included;

@@ -209,15 +209,10 @@ int ldp_restrict_variants(ldp_engine* e, const uint64_t* keep_bitmap, uint32_t k
     }
   }
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
   e->rows_compacted = moved;
   e->rows_direct = direct;
   e->rows_bounced = bounced;
-  e->ms_compact = ms;
+  e->ms_compact = ev.elapsed_ms(0, 1);
   // ---- plan again: the plan-sized arrays go, the image stays (its tail is unused until ldp_release_device())
   free_device(e, true);
   if (!codes) {

@@ -1,7 +1,6 @@
 // ldp_engine_sample_het.cpp -- ldp_sample_het_counts(): per-sample het-call counts, missing-call counts and weighted missing-call sums of
 // loaded rows, read from the resident 2-bit image (ldp_sample_het.hip).  Contract, states and refusals are those of
-// ldp_sample_missing_counts(): nothing of the engine changes, before as after ldp_restrict_variants(), and the requested variants are walked
-// as the runs of consecutive image rows the engine owns them in (one launch per run).  include / weight are the caller's per-variant arrays of
+// resident_runs() (ldp_engine.cpp), with the image: one launch per run of owned rows.  include / weight are the caller's per-variant arrays of
 // the range; each launch gets them from its run's first variant on.
 // (host runtime behind include/ldprune_hip.h; ldp_engine.cpp has the overview)
 #include "ldp_engine_internal.h"
@@ -30,43 +29,10 @@ int sample_het_counts_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
   if (weight && !missing_weight) {
     return fail(e, LDP_ERR_INVALID, "weight given but missing_weight is NULL");
   }
-  if (static_cast<uint64_t>(first_variant) + n > e->variant_ct) {
-    return fail(e, LDP_ERR_INVALID, "variant range out of bounds");
-  }
-  if (e->world > 1) {
-    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_sample_het_counts() on a sharded engine (ldp_set_shard with world > 1)");
-  }
-  if ((e->P.founder_ct > kMfMaxFounders) || !e->opt.pair_mfma || (e->plan_uploaded && !e->codes_format)) {
-    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_sample_het_counts() on an engine that keeps bit-planes (no 2-bit code image)");
-  }
-  if (e->loaded_special) {
-    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_sample_het_counts() on rows loaded as LDP_GENO_PHASED or through a sample map that makes het calls missing");
-  }
-  const uint32_t end = first_variant + n;
-  struct Run {
-    uint32_t l_first, ct, off;  // image row, rows, first variant's offset in the range
-  };
-  std::vector<Run> runs;
-  uint32_t covered = 0;
-  for (const ldp_engine::OwnedRun& r : e->owned_runs) {
-    const uint32_t a = std::max(r.g_first, first_variant), b = std::min(r.g_end, end);
-    if (a < b) {
-      runs.push_back({static_cast<uint32_t>(e->global_to_local[a]), b - a, a - first_variant});
-      covered += b - a;
-    }
-  }
-  if (covered != n) {
-    return fail(e, LDP_ERR_STATE, "a variant of the range has no row in this engine (its plan did not own it)");
-  }
-  if (n && !e->plan_uploaded) {
-    return fail(e, LDP_ERR_STATE, "nothing is loaded");
-  }
-  for (const Run& r : runs) {
-    for (uint32_t l = r.l_first; l < r.l_first + r.ct; ++l) {
-      if (!e->loaded[l]) {
-        return fail(e, LDP_ERR_STATE, "genotypes missing for a variant of the range (ldp_load_genotypes)");
-      }
-    }
+  std::vector<ResidentRun> runs;
+  int rc = resident_runs(e, "ldp_sample_het_counts()", first_variant, n, true, &runs);
+  if (rc) {
+    return rc;
   }
   const uint32_t founder_ct = e->P.founder_ct;
   memset(het_ct, 0, static_cast<size_t>(founder_ct) * sizeof(uint32_t));
@@ -77,9 +43,10 @@ int sample_het_counts_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
   if (!n) {
     return LDP_OK;
   }
-  HIP_TRY(e, hipSetDevice(e->device));
-  // the count pass of the loads (it writes each row's padding, and inverts ALT-major rows) is finished before the rows are read
-  HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+  rc = begin_resident_read(e);
+  if (rc) {
+    return rc;
+  }
   // one allocation: missing_weight | weight (64-bit), het_ct | missing_ct (32-bit), include (bytes)
   const size_t fc = founder_ct;
   const size_t off_w = fc * 8, off_het = off_w + (weight ? static_cast<size_t>(n) * 8 : 0), off_mis = off_het + fc * 4, off_inc = off_mis + fc * 4;
@@ -104,7 +71,7 @@ int sample_het_counts_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
   }
   HIP_TRY(e, hipEventRecord(ev.ev[0], e->stream));
   uint64_t bytes = 0;
-  for (const Run& r : runs) {
+  for (const ResidentRun& r : runs) {
     const hipError_t krc = launch_sample_het(e->d_codes, e->code_row_bytes, r.l_first, r.ct, founder_ct, d_inc ? d_inc + r.off : nullptr, d_weight ? d_weight + r.off : nullptr, d_het,
                                              d_mis, d_weight ? d_mw : nullptr, slab_rows, e->stream);
     if (krc != hipSuccess) {
@@ -119,13 +86,8 @@ int sample_het_counts_impl(ldp_engine* e, uint32_t first_variant, uint32_t n, co
     HIP_TRY(e, hipMemcpyAsync(missing_weight, d_mw, fc * 8, hipMemcpyDeviceToHost, e->stream));
   }
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
   if (ms_kernel) {
-    *ms_kernel = ms;
+    *ms_kernel = ev.elapsed_ms(0, 1);
   }
   if (bytes_read) {
     *bytes_read = bytes;

@@ -3,6 +3,31 @@
 
 namespace p2h {
 
+namespace {
+
+// one bit per sample of the file (bit s & 7 of byte s >> 3), set where keep(s)
+template <class Keep>
+std::vector<uint8_t> sample_mask(uint32_t raw_sample_ct, Keep keep) {
+  std::vector<uint8_t> mask((static_cast<size_t>(raw_sample_ct) + 7) / 8, 0);
+  for (uint32_t s = 0; s < raw_sample_ct; ++s) {
+    if (keep(s)) {
+      mask[s >> 3] |= static_cast<uint8_t>(1u << (s & 7));
+    }
+  }
+  return mask;
+}
+
+// x = min(x, v)
+void atomic_min(std::atomic<uint32_t>* x, uint32_t v) {
+  uint32_t cur = x->load();
+  while ((v < cur) && !x->compare_exchange_weak(cur, v)) {
+  }
+}
+
+double gb_per_s(double bytes, double seconds) { return (seconds > 0.0) ? (bytes / 1e9 / seconds) : 0.0; }
+
+}  // namespace
+
 // ---- --indep-pairwise / --indep-pairphase ----
 void Session::need_dosage_sums(const std::vector<uint32_t>& raw_variants) {
   std::vector<uint32_t> todo;
@@ -14,12 +39,7 @@ void Session::need_dosage_sums(const std::vector<uint32_t>& raw_variants) {
   if (todo.empty()) {
     return;
   }
-  std::vector<uint8_t> founder_mask((static_cast<size_t>(raw_sample_ct) + 7) / 8, 0);
-  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-    if (is_founder[sx]) {
-      founder_mask[sx >> 3] |= static_cast<uint8_t>(1u << (sx & 7));
-    }
-  }
+  const std::vector<uint8_t> founder_mask = sample_mask(raw_sample_ct, [&](uint32_t s) { return is_founder[s] != 0; });
   const uint8_t* mask = (founder_ct == raw_sample_ct) ? nullptr : founder_mask.data();
   std::vector<std::pair<uint64_t, uint64_t>> out(todo.size());
   std::atomic<uint32_t> next(0);
@@ -105,6 +125,26 @@ struct PruneJob {
 
   [[noreturn]] void die_unphased(uint32_t raw_v) const {
     die(7, "\nError: --indep-pairphase: 0-based variant #%u is not fully phased.\n", raw_v);  // plink2_ld.cc:2047
+  }
+  // a library call that has to succeed: otherwise the engine's message and exit 16
+  static void must(ldp_engine* e, int rc) {
+    if (rc) {
+      die(16, "\nError: %s\n", ldp_last_error(e));
+    }
+  }
+  // all m_ct records of an engine
+  std::vector<ldp_variant_rec> recs_of(ldp_engine* e) const {
+    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
+    must(e, ldp_get_variant_recs(e, 0, m_ct, recs.data()));
+    return recs;
+  }
+  // per-column values of the image into file sample order (column f of the image is founder f of the file: every kept sample is a founder here)
+  template <class T>
+  void to_file_order(const std::vector<T>& by_column, std::vector<T>* per_sample) const {
+    per_sample->assign(raw_sample_ct, 0);
+    for (uint32_t f = 0; f < founder_ct; ++f) {
+      (*per_sample)[founder_idx[f]] = by_column[f];
+    }
   }
   // --indep-preferred bits of a subset of the variants (ks: include-order indices, in the subset's engine order)
   std::vector<uint64_t> sub_preferred(const std::vector<uint32_t>& ks) const {
@@ -297,12 +337,7 @@ struct PruneJob {
     // mapping: a 12 GB mapping is faulted in page run by page run, and what that costs swung between 0.35 and 0.97 s from one run to
     // the next on the same host, while 32 readers take 0.36-0.38 s every time (--debug-load-map: the mapping)
     direct_fd = (direct && !g_dbg.load_map) ? ldp_pgen_direct_fd(pg, &direct_off, nullptr) : -1;
-    founder_mask.assign((static_cast<size_t>(raw_sample_ct) + 7) / 8, 0);
-    for (uint32_t sidx = 0; sidx < raw_sample_ct; ++sidx) {
-      if (is_founder[sidx]) {
-        founder_mask[sidx >> 3] |= static_cast<uint8_t>(1u << (sidx & 7));
-      }
-    }
+    founder_mask = sample_mask(raw_sample_ct, [&](uint32_t s) { return is_founder[s] != 0; });
     founder_idx.clear();
     for (uint32_t s = 0; s < raw_sample_ct; ++s) {
       if (is_founder[s]) {
@@ -341,9 +376,7 @@ struct PruneJob {
     const bool device_subset = (!all_founders) && !A.pairphase;
     if (device_subset) {
       for (int r = 0; r < world; ++r) {
-        if (ldp_set_sample_map(eng[r], raw_sample_ct, founder_idx.data(), nullptr)) {
-          die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-        }
+        must(eng[r], ldp_set_sample_map(eng[r], raw_sample_ct, founder_idx.data(), nullptr));
       }
     }
     // Variable-width records are decoded ON THE DEVICE from the file's own bytes (ldp_load_pgen_records: main track of every
@@ -358,7 +391,42 @@ struct PruneJob {
     device_multi = device_decode && (all_founders || device_subset);
     uint64_t file_size = 0;
     const void* file_bytes = device_decode ? ldp_pgen_file_bytes(pg, &file_size) : nullptr;
-    std::vector<ldp_pgen_rec> rec_index;
+    // What the device decoder wants of a run: its record index, the record an LD-compressed chain starts from when that lies in front of the
+    // run, and the allele count of every record that is to be collapsed.  0, or the exit code with its message (a feeding thread must not die).
+    struct RunIndex {
+      std::vector<ldp_pgen_rec> recs;
+      uint32_t base_v = UINT32_MAX;
+      ldp_pgen_rec base_rec;
+      const ldp_pgen_rec* base() const { return (base_v != UINT32_MAX) ? &base_rec : nullptr; }
+    };
+    auto index_run = [&](const Run& rn, RunIndex* ix, std::string* err) -> int {
+      ix->recs.resize(rn.n);
+      ix->base_v = UINT32_MAX;
+      if (ldp_pgen_record_index(pg, rn.raw0, rn.n, ix->recs.data(), &ix->base_v) || ((ix->base_v != UINT32_MAX) && ldp_pgen_record_index(pg, ix->base_v, 1, &ix->base_rec, nullptr))) {
+        *err = gpath + ": malformed variant record index.";
+        return 6;
+      }
+      for (uint32_t t = 0; device_multi && (t < rn.n); ++t) {
+        const uint32_t alts = V.alt_ct[rn.raw0 + t];
+        if ((alts > 1) && (vcls[mk[rn.q + t]] != 5)) {
+          if (alts > 254) {
+            *err = "variant '" + V.id[rn.raw0 + t] + "' has more than 254 ALT alleles: not supported by plink2-hip.";
+            return 63;
+          }
+          ix->recs[t].allele_ct = static_cast<uint8_t>(alts + 1);
+        }
+      }
+      return 0;
+    };
+    // Rows of a run to an engine.  Fixed-width rows as the file has them go with pread() straight into the engine's pinned ring
+    // (ldp_load_genotypes_fd); decoded or gathered rows, and the mapping under --debug-load-map, from memory.  The library's return code.
+    auto load_rows = [&](ldp_engine* e, const Run& rn, const uint8_t* src, uint64_t stride) -> int {
+      const int enc = load_encoding | (device_subset ? LDP_GENO_MAPPED : 0);
+      const uint64_t file_off = static_cast<uint64_t>(rn.raw0) * rec_bytes;
+      const bool from_fd = direct && (src == direct + file_off) && (direct_fd >= 0);
+      return from_fd ? ldp_load_genotypes_fd(e, rn.q, rn.n, direct_fd, direct_off + file_off, stride, enc) : ldp_load_genotypes(e, rn.q, rn.n, src, stride, LDP_MEM_HOST, enc);
+    };
+    RunIndex rec_index;
     std::thread decoder;
     // The decoder runs beside the engine's copy threads (ldp_load_genotypes: 16 of them feeding the pinned ring); a record
     // takes microseconds, so a few dozen threads keep ahead of PCIe and more only get in the copies' way.
@@ -394,7 +462,7 @@ struct PruneJob {
             st.node = bind_near_device(r % n_devices, &before);
           }
           (void)ldp_use_private_copy_threads(eng[r]);
-          std::vector<ldp_pgen_rec> idx;
+          RunIndex idx;
           size_t at = 0;  // first range of mine[r] that may still reach the current run
           for (const Run& rn : runs) {
             while ((at < mine[r].size()) && (mine[r][at].second <= rn.q)) {
@@ -411,44 +479,21 @@ struct PruneJob {
             if (st.t0 < 0.0) {
               st.t0 = tc;
             }
-            int rc;
             if (device_decode) {
-              idx.resize(rn.n);
-              uint32_t base_v = UINT32_MAX;
-              ldp_pgen_rec base_rec;
-              if (ldp_pgen_record_index(pg, rn.raw0, rn.n, idx.data(), &base_v) || ((base_v != UINT32_MAX) && ldp_pgen_record_index(pg, base_v, 1, &base_rec, nullptr))) {
-                st.rc = 6;
-                st.err = gpath + ": malformed variant record index.";
+              st.rc = index_run(rn, &idx, &st.err);
+              if (st.rc) {
                 return;
               }
-              if (device_multi) {
-                for (uint32_t t = 0; t < rn.n; ++t) {
-                  const uint32_t alts = V.alt_ct[rn.raw0 + t];
-                  if ((alts > 1) && (vcls[mk[rn.q + t]] != 5)) {
-                    if (alts > 254) {
-                      st.rc = 63;
-                      st.err = "variant '" + V.id[rn.raw0 + t] + "' has more than 254 ALT alleles: not supported by plink2-hip.";
-                      return;
-                    }
-                    idx[t].allele_ct = static_cast<uint8_t>(alts + 1);
-                  }
-                }
-              }
-              rc = ldp_load_pgen_records(eng[r], rn.q, rn.n, file_bytes, file_size, LDP_MEM_HOST, idx.data(), (base_v != UINT32_MAX) ? &base_rec : nullptr, raw_sample_ct, nullptr);
+              const int rc = ldp_load_pgen_records(eng[r], rn.q, rn.n, file_bytes, file_size, LDP_MEM_HOST, idx.recs.data(), idx.base(), raw_sample_ct, nullptr);
               if (rc) {
                 st.rc = (rc == LDP_ERR_INVALID) ? 6 : 16;
                 st.err = gpath + ": " + ldp_last_error(eng[r]);
                 return;
               }
-            } else {
-              const int enc = load_encoding | (device_subset ? LDP_GENO_MAPPED : 0);
-              rc = (direct_fd >= 0) ? ldp_load_genotypes_fd(eng[r], rn.q, rn.n, direct_fd, direct_off + static_cast<uint64_t>(rn.raw0) * rec_bytes, in_rec, enc)
-                                    : ldp_load_genotypes(eng[r], rn.q, rn.n, direct + static_cast<uint64_t>(rn.raw0) * rec_bytes, in_rec, LDP_MEM_HOST, enc);
-              if (rc) {
-                st.rc = 16;
-                st.err = ldp_last_error(eng[r]);
-                return;
-              }
+            } else if (load_rows(eng[r], rn, direct + static_cast<uint64_t>(rn.raw0) * rec_bytes, in_rec)) {
+              st.rc = 16;
+              st.err = ldp_last_error(eng[r]);
+              return;
             }
             st.t1 = now_s();
             st.rows += owned_rows;
@@ -476,7 +521,7 @@ struct PruneJob {
           }
           logprintf("\n[timing] engine %d (device %d, NUMA node %d): fed %.3f - %.3f s (%.3f s), %llu rows in %llu calls, %.1f GB/s", r, r % n_devices, st.node,
                     st.t0 - t_begin, st.t1 - t_begin, st.t1 - st.t0, static_cast<unsigned long long>(st.rows), static_cast<unsigned long long>(st.calls),
-                    (st.t1 > st.t0) ? (static_cast<double>(st.rows) * static_cast<double>(direct ? rec_bytes : out_rec) / (st.t1 - st.t0) / 1e9) : 0.0);
+                    gb_per_s(static_cast<double>(st.rows) * static_cast<double>(direct ? rec_bytes : out_rec), st.t1 - st.t0));
           busy_sum += st.t1 - st.t0;
           span0 = std::min(span0, st.t0);
           span1 = std::max(span1, st.t1);
@@ -518,30 +563,15 @@ struct PruneJob {
       const uint8_t* src;
       uint64_t stride = in_rec;
       if (device_decode) {
-        rec_index.resize(run);
-        uint32_t base_v = UINT32_MAX;
-        ldp_pgen_rec base_rec;
-        if (ldp_pgen_record_index(pg, raw0, run, rec_index.data(), &base_v) || ((base_v != UINT32_MAX) && ldp_pgen_record_index(pg, base_v, 1, &base_rec, nullptr))) {
-          die(6, "\nError: %s: malformed variant record index.\n", gpath.c_str());
-        }
-        if (device_multi) {
-          for (uint32_t t = 0; t < run; ++t) {
-            const uint32_t alts = V.alt_ct[raw0 + t];
-            if ((alts > 1) && (vcls[mk[q + t]] != 5)) {
-              if (alts > 254) {
-                die(63, "\nError: variant '%s' has more than 254 ALT alleles: not supported by plink2-hip.\n", V.id[raw0 + t].c_str());
-              }
-              rec_index[t].allele_ct = static_cast<uint8_t>(alts + 1);
-            }
-          }
+        std::string err;
+        if (const int code = index_run(runs[k], &rec_index, &err)) {
+          die(code, "\nError: %s\n", err.c_str());
         }
         const double tl0 = now_s();
         for (int r = 0; r < world; ++r) {
           uint32_t bad_q = UINT32_MAX;
-          const int rc = device_phase ? ldp_load_pgen_records_phased(eng[r], q, run, file_bytes, file_size, LDP_MEM_HOST, rec_index.data(),
-                                                                     (base_v != UINT32_MAX) ? &base_rec : nullptr, raw_sample_ct, &bad_q)
-                                      : ldp_load_pgen_records(eng[r], q, run, file_bytes, file_size, LDP_MEM_HOST, rec_index.data(),
-                                                              (base_v != UINT32_MAX) ? &base_rec : nullptr, raw_sample_ct, nullptr);
+          const int rc = device_phase ? ldp_load_pgen_records_phased(eng[r], q, run, file_bytes, file_size, LDP_MEM_HOST, rec_index.recs.data(), rec_index.base(), raw_sample_ct, &bad_q)
+                                      : ldp_load_pgen_records(eng[r], q, run, file_bytes, file_size, LDP_MEM_HOST, rec_index.recs.data(), rec_index.base(), raw_sample_ct, nullptr);
           if ((rc == LDP_ERR_UNPHASED) && (bad_q != UINT32_MAX)) {
             die_unphased(inc[mk[bad_q]]);  // (chunks and launches run in variant order: the first one to fail holds the lowest variant)
           }
@@ -580,13 +610,7 @@ struct PruneJob {
       }
       const double tl0 = now_s();
       for (int r = 0; r < world; ++r) {
-        // fixed-width rows as the file has them: with pread() straight into the engine's
-        // pinned ring (ldp_load_genotypes_fd)
-        const bool from_fd = direct && (src == direct + static_cast<uint64_t>(raw0) * rec_bytes) && (direct_fd >= 0);
-        const int rc = from_fd ? ldp_load_genotypes_fd(eng[r], q, run, direct_fd, direct_off + static_cast<uint64_t>(raw0) * rec_bytes, stride,
-                                                       load_encoding | (device_subset ? LDP_GENO_MAPPED : 0))
-                               : ldp_load_genotypes(eng[r], q, run, src, stride, LDP_MEM_HOST, load_encoding | (device_subset ? LDP_GENO_MAPPED : 0));
-        if (rc) {
+        if (load_rows(eng[r], runs[k], src, stride)) {
           die(16, "Error: %s\n", ldp_last_error(eng[r]));
         }
       }
@@ -624,9 +648,7 @@ struct PruneJob {
         ref_is_major.assign(m_ct, 0);
         std::vector<ldp_variant_rec> recs(m_ct);
         for (int r = 0; r < world; ++r) {  // (a variant's counts are zero on the engines that do not own it)
-          if (ldp_get_variant_recs(eng[r], 0, m_ct, recs.data())) {
-            die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-          }
+          must(eng[r], ldp_get_variant_recs(eng[r], 0, m_ct, recs.data()));
           for (uint32_t qq = 0; qq < m_ct; ++qq) {
             const uint64_t ref_ct = 2ull * recs[qq].n_homref + recs[qq].n_het;
             const uint64_t tot = 2ull * (static_cast<uint64_t>(recs[qq].n_homref) + recs[qq].n_het + recs[qq].n_homalt);
@@ -676,10 +698,8 @@ struct PruneJob {
         ++multi_ct;
       }
       for (int r = 0; r < world; ++r) {
-        if (ldp_load_genotypes(eng[r], qq, 1, inv_row.data(), host_rec, LDP_MEM_HOST, LDP_GENO_INVERSE) ||
-            ldp_set_maj_freqs(eng[r], qq, 1, &mf)) {
-          die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-        }
+        must(eng[r], ldp_load_genotypes(eng[r], qq, 1, inv_row.data(), host_rec, LDP_MEM_HOST, LDP_GENO_INVERSE));
+        must(eng[r], ldp_set_maj_freqs(eng[r], qq, 1, &mf));
       }
     }
     if (std::min(multi_unphased, pending_unphased) != UINT32_MAX) {
@@ -727,9 +747,7 @@ struct PruneJob {
           std::vector<uint8_t> has(q_n), any(q_n, 0);
           std::vector<std::pair<uint64_t, uint64_t>> got(q_n);
           for (int r = 0; (r < world) && !g_dbg.host_decode; ++r) {
-            if (ldp_get_dosage_sums(eng[r], q_lo, q_n, ref_dd.data(), alt_dd.data(), has.data())) {
-              die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-            }
+            must(eng[r], ldp_get_dosage_sums(eng[r], q_lo, q_n, ref_dd.data(), alt_dd.data(), has.data()));
             for (uint32_t k = 0; k < q_n; ++k) {
               if (has[k] && !any[k]) {
                 any[k] = 1;
@@ -766,9 +784,7 @@ struct PruneJob {
           ++run;
         }
         for (int r = 0; r < world; ++r) {
-          if (ldp_set_maj_freqs(eng[r], todo[q], static_cast<uint32_t>(run), &mfs[q])) {
-            die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-          }
+          must(eng[r], ldp_set_maj_freqs(eng[r], todo[q], static_cast<uint32_t>(run), &mfs[q]));
         }
         q += run;
       }
@@ -790,13 +806,9 @@ struct PruneJob {
       die(16, "\nError: internal: --mind counted %u variants on the host's list and %u rows are loaded.\n", S.mind_variant_ct, m_ct);
     }
     std::vector<uint32_t> by_column(std::max<uint32_t>(founder_ct, 1), 0);
-    if (ldp_sample_missing_counts(eng[0], 0, m_ct, by_column.data())) {
-      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-    }
-    std::vector<uint32_t> missing_cts(raw_sample_ct, 0);
-    for (uint32_t f = 0; f < founder_ct; ++f) {
-      missing_cts[founder_idx[f]] = by_column[f];  // (column f of the image is founder f of the file: every kept sample is a founder here)
-    }
+    must(eng[0], ldp_sample_missing_counts(eng[0], 0, m_ct, by_column.data()));
+    std::vector<uint32_t> missing_cts;
+    to_file_order(by_column, &missing_cts);
     std::vector<uint8_t> removed_samples;
     const uint32_t removed_ct = mind_decide(S, missing_cts, &removed_samples);
     if (A.timing) {
@@ -804,7 +816,7 @@ struct PruneJob {
       uint64_t bytes = 0;
       (void)ldp_debug_get_sample_missing_stats(eng[0], &ms, &bytes);
       logprintf("[timing] sample filter (--mind): from the resident image (%u rows, %.3f ms = %.0f GB/s; %u sample%s removed%s)\n", m_ct, ms,
-                (ms > 0.0) ? (static_cast<double>(bytes) / 1e9 / (ms * 1e-3)) : 0.0, removed_ct, (removed_ct == 1) ? "" : "s", removed_ct ? ", reloading" : "");
+                gb_per_s(static_cast<double>(bytes), ms * 1e-3), removed_ct, (removed_ct == 1) ? "" : "s", removed_ct ? ", reloading" : "");
     }
     if (!removed_ct) {
       return false;
@@ -828,10 +840,7 @@ struct PruneJob {
     if ((m_ct != S.report_variants.size()) || (m_ct != variant_ct)) {
       die(16, "\nError: internal: the reports list %zu variants and %u rows are loaded.\n", S.report_variants.size(), m_ct);
     }
-    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
-    if (ldp_get_variant_recs(eng[0], 0, m_ct, recs.data())) {
-      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-    }
+    const std::vector<ldp_variant_rec> recs = recs_of(eng[0]);
     ReportCounts C;
     C.kept_sample_ct = founder_ct;
     C.variants.resize(m_ct);
@@ -856,9 +865,7 @@ struct PruneJob {
     if (offsets[m_ct]) {
       std::vector<uint32_t> counts(offsets[m_ct]);
       std::vector<uint8_t> has(m_ct), lo, hi;
-      if (ldp_get_allele_counts(eng[0], 0, m_ct, offsets.data(), counts.data(), has.data())) {
-        die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-      }
+      must(eng[0], ldp_get_allele_counts(eng[0], 0, m_ct, offsets.data(), counts.data(), has.data()));
       for (uint32_t q = 0; q < m_ct; ++q) {
         if (offsets[q + 1] == offsets[q]) {
           continue;
@@ -876,12 +883,8 @@ struct PruneJob {
     C.sample_missing.assign(raw_sample_ct, 0);
     if (A.rep_smiss()) {
       std::vector<uint32_t> by_column(std::max<uint32_t>(founder_ct, 1), 0);
-      if (ldp_sample_missing_counts(eng[0], 0, m_ct, by_column.data())) {
-        die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-      }
-      for (uint32_t f = 0; f < founder_ct; ++f) {
-        C.sample_missing[founder_idx[f]] = by_column[f];  // (column f of the image is founder f of the file: every kept sample is a founder here)
-      }
+      must(eng[0], ldp_sample_missing_counts(eng[0], 0, m_ct, by_column.data()));
+      to_file_order(by_column, &C.sample_missing);
     }
     const double t1 = now_s();
     write_reports(S, C);
@@ -902,10 +905,7 @@ struct PruneJob {
       die(16, "\nError: internal: --het lists %u variants and %u rows are loaded.\n", variant_ct, m_ct);
     }
     het_preamble(S, m_ct, 0);
-    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
-    if (ldp_get_variant_recs(eng[0], 0, m_ct, recs.data())) {
-      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-    }
+    const std::vector<ldp_variant_rec> recs = recs_of(eng[0]);
     std::vector<double> ehet(m_ct, 0.0);
     std::vector<uint8_t> ok(m_ct, 0);
     for (uint32_t q = 0; q < m_ct; ++q) {
@@ -923,24 +923,17 @@ struct PruneJob {
     double ms = 0.0;
     uint64_t bytes = 0;
     // (--timing: the same pass through its measurement hook, which also returns the kernel's time and the bytes it read)
-    if (A.timing ? ldp_debug_sample_het_counts(eng[0], 0, m_ct, plan.include.data(), plan.weight.data(), het_col.data(), mis_col.data(), mw_col.data(), 0, &ms, &bytes)
-                 : ldp_sample_het_counts(eng[0], 0, m_ct, plan.include.data(), plan.weight.data(), het_col.data(), mis_col.data(), mw_col.data())) {
-      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-    }
+    must(eng[0], A.timing ? ldp_debug_sample_het_counts(eng[0], 0, m_ct, plan.include.data(), plan.weight.data(), het_col.data(), mis_col.data(), mw_col.data(), 0, &ms, &bytes)
+                          : ldp_sample_het_counts(eng[0], 0, m_ct, plan.include.data(), plan.weight.data(), het_col.data(), mis_col.data(), mw_col.data()));
     HetSums sums;
-    sums.het_ct.assign(raw_sample_ct, 0);
-    sums.missing_ct.assign(raw_sample_ct, 0);
-    sums.missing_weight.assign(raw_sample_ct, 0);
-    for (uint32_t f = 0; f < founder_ct; ++f) {
-      sums.het_ct[founder_idx[f]] = het_col[f];
-      sums.missing_ct[founder_idx[f]] = mis_col[f];
-      sums.missing_weight[founder_idx[f]] = mw_col[f];
-    }
+    to_file_order(het_col, &sums.het_ct);
+    to_file_order(mis_col, &sums.missing_ct);
+    to_file_order(mw_col, &sums.missing_weight);
     const double t1 = now_s();
     het_write(S, plan, sums);
     if (A.timing) {
       logprintf("[timing] --het: from the resident image (%u rows, %u of them kept; kernel %.3f ms = %.0f GB/s; records, plan and the call %.3f s, writing %.3f s)\n", m_ct, plan.kept, ms,
-                (ms > 0.0) ? (static_cast<double>(bytes) / 1e9 / (ms * 1e-3)) : 0.0, t1 - t0, now_s() - t1);
+                gb_per_s(static_cast<double>(bytes), ms * 1e-3), t1 - t0, now_s() - t1);
     }
   }
   void het_stage() {
@@ -985,9 +978,7 @@ struct PruneJob {
         }
         uint64_t found = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
-          if (ldp_king_block_hits(eng[0], 0, m_ct, nullptr, r0, rows, 0, cols, A.king_filter, hits.data(), hits.size(), &found)) {
-            die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-          }
+          must(eng[0], ldp_king_block_hits(eng[0], 0, m_ct, nullptr, r0, rows, 0, cols, A.king_filter, hits.data(), hits.size(), &found));
           if (found <= hits.size()) {
             break;
           }
@@ -1004,9 +995,7 @@ struct PruneJob {
         dense.resize(static_cast<size_t>(rows) * cols);
         double ms = 0.0;
         uint64_t pv = 0;
-        if (ldp_debug_king_counts_block(eng[0], 0, m_ct, nullptr, r0, rows, 0, cols, dense.data(), cols, 0, &ms, &pv)) {
-          die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-        }
+        must(eng[0], ldp_debug_king_counts_block(eng[0], 0, m_ct, nullptr, r0, rows, 0, cols, dense.data(), cols, 0, &ms, &pv));
         call_s += now_s() - tc;
         ms_total += ms;
         pair_variants += pv;
@@ -1046,10 +1035,7 @@ struct PruneJob {
   // tables follow.  One engine, autosomes only, no multiallelic variant: mk is every variant.
   void filter_on_device() {
     const double t0 = now_s();
-    std::vector<ldp_variant_rec> recs(std::max<uint32_t>(m_ct, 1));
-    if (ldp_get_variant_recs(eng[0], 0, m_ct, recs.data())) {
-      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-    }
+    const std::vector<ldp_variant_rec> recs = recs_of(eng[0]);
     CountFilters F(A, S.kept_sample_ct);
     // --hwe / --hardy: ln p of every row from the same records, where they lie (hwe_kernel through ldp_hwe_ln_pvals: no copy of the records,
     // no host thread); one call serves both where their `midp` settings agree.  (--timing: the call through its measurement hook)
@@ -1060,9 +1046,7 @@ struct PruneJob {
       auto pvals = [&](int midp, std::vector<double>* out) {
         out->assign(std::max<uint32_t>(m_ct, 1), 0.0);
         double ms = 0.0;
-        if (ldp_debug_hwe_ln_pvals(eng[0], 0, m_ct, midp, out->data(), flags.data(), &ms)) {
-          die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-        }
+        must(eng[0], ldp_debug_hwe_ln_pvals(eng[0], 0, m_ct, midp, out->data(), flags.data(), &ms));
         hwe_ms_kernel += ms;
         hwe_pvals += m_ct;
         for (uint32_t q = 0; q < m_ct; ++q) {
@@ -1127,9 +1111,7 @@ struct PruneJob {
         die(6, "Error: When the window size is in kb units, LD-based pruning requires a sorted\n.pvar/.bim.  Retry this command after using --make-pgen/--make-bed +\n--sort-vars to sort your data.\n");
       }
     }
-    if (ldp_restrict_variants(eng[0], keep.data(), kept, m_chr.data(), A.window_is_bp ? m_bps.data() : nullptr)) {
-      die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-    }
+    must(eng[0], ldp_restrict_variants(eng[0], keep.data(), kept, m_chr.data(), A.window_is_bp ? m_bps.data() : nullptr));
     ldp_get_subcontigs(eng[0], &subcontig_ct, nullptr, 0);
     (void)ldp_debug_get_compact_stats(eng[0], &filter_rows_compacted, nullptr, &filter_rows_bounced, &filter_ms_compact);
     removed.assign((static_cast<size_t>(variant_ct) + 63) / 64 + 1, 0);
@@ -1189,9 +1171,7 @@ struct PruneJob {
     th.clear();
     // (a rank whose run failed must not leave the others waiting in a collective: nobody enters it then)
     for (int r = 0; r < world; ++r) {
-      if (rcs[r]) {
-        die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-      }
+      must(eng[r], rcs[r]);
     }
     if (world == 1) {
       scatter(part[0], mk);
@@ -1214,18 +1194,14 @@ struct PruneJob {
           t.join();
         }
         for (int r = 0; r < world; ++r) {
-          if (rcs[r]) {  // (the failing rank aborted its communicator; the process ends here, nothing is destroyed twice)
-            die(16, "\nError: %s\n", ldp_last_error(eng[r]));
-          }
+          must(eng[r], rcs[r]);  // (the failing rank aborted its communicator; the process ends here, nothing is destroyed twice)
         }
         for (int r = 0; r < world; ++r) {
           ldp_comm_destroy(comms[r]);
         }
       } else {
         uint64_t seg_words = 0;
-        if (ldp_shard_segment_words(eng[0], &seg_words)) {
-          die(16, "\nError: %s\n", ldp_last_error(eng[0]));
-        }
+        must(eng[0], ldp_shard_segment_words(eng[0], &seg_words));
         std::vector<uint64_t> segs(static_cast<size_t>(seg_words) * world, 0);
         for (int r = 0; r < world; ++r) {
           if (ldp_pack_removed_segment(eng[r], part[r].data(), segs.data() + static_cast<size_t>(r) * seg_words)) {
@@ -1290,11 +1266,8 @@ struct PruneJob {
       sp.x_freq = (which == 0);
       const bool x_phased = A.pairphase && (which == 0) && !sp.part2.empty();
       std::vector<uint8_t> nonmale_mask;
-      if (x_phased) {
-        nonmale_mask.assign((static_cast<size_t>(raw_sample_ct) + 7) / 8, 0);
-        for (uint32_t sidx : sp.part2) {
-          nonmale_mask[sidx >> 3] |= static_cast<uint8_t>(1u << (sidx & 7));
-        }
+      if (x_phased) {  // (sp.part2: the founders that are not male)
+        nonmale_mask = sample_mask(raw_sample_ct, [&](uint32_t s) { return is_founder[s] && (sex[s] != 1); });
       }
       const uint32_t fct = sp.out_ct();
       if (fct < 2) {
@@ -1335,9 +1308,7 @@ struct PruneJob {
             het_missing.push_back(0);
           }
         }
-        if (ldp_set_sample_map(se, raw_sample_ct, src_sample.data(), het_missing.data())) {
-          die(16, "\nError: %s\n", ldp_last_error(se));
-        }
+        must(se, ldp_set_sample_map(se, raw_sample_ct, src_sample.data(), het_missing.data()));
         const uint32_t max_run = std::max<uint32_t>(1, static_cast<uint32_t>((256ull << 20) / std::max<uint64_t>(rec_bytes, 1)));
         std::vector<uint8_t> decoded;
         for (uint32_t w0 = 0; w0 < ks.size();) {
@@ -1356,9 +1327,7 @@ struct PruneJob {
             }
             rows_at = decoded.data();
           }
-          if (ldp_load_genotypes(se, w0, run, rows_at, rec_bytes, LDP_MEM_HOST, encoding | LDP_GENO_MAPPED)) {
-            die(16, "\nError: %s\n", ldp_last_error(se));
-          }
+          must(se, ldp_load_genotypes(se, w0, run, rows_at, rec_bytes, LDP_MEM_HOST, encoding | LDP_GENO_MAPPED));
           w0 += run;
         }
         // variants with several ALT alleles: their rows (collapsed on the major allele of the chromosome's own allele-frequency rule) are
@@ -1376,9 +1345,8 @@ struct PruneJob {
           }
           double mf = 0.0;
           multiallelic_sex_row(pg, raw_v, V.alt_ct[raw_v], sp, &lo_a, &hi_a, m_row.data(), s_rec, &mf);
-          if (ldp_load_genotypes(se, w, 1, m_row.data(), s_rec, LDP_MEM_HOST, LDP_GENO_INVERSE) || ldp_set_maj_freqs(se, w, 1, &mf)) {
-            die(16, "\nError: %s\n", ldp_last_error(se));
-          }
+          must(se, ldp_load_genotypes(se, w, 1, m_row.data(), s_rec, LDP_MEM_HOST, LDP_GENO_INVERSE));
+          must(se, ldp_set_maj_freqs(se, w, 1, &mf));
         }
       }
       for (uint32_t w0 = 0; x_phased && (w0 < ks.size()); w0 += chunk) {
@@ -1403,9 +1371,7 @@ struct PruneJob {
                 multiallelic_sex_row_phased(pg, raw_v, V.alt_ct[raw_v], sp, &lo_a, &hi_a, ph_a.data(), ph_a.size() / 2, rows.data() + static_cast<uint64_t>(w) * s_rec, s_rec,
                                             &mfs[w], &unph);
                 if (unph) {
-                  uint32_t cur = x_unphased.load();
-                  while ((raw_v < cur) && !x_unphased.compare_exchange_weak(cur, raw_v)) {
-                  }
+                  atomic_min(&x_unphased, raw_v);
                 }
                 continue;
               }
@@ -1413,9 +1379,7 @@ struct PruneJob {
                 uint32_t at = 0;
                 const int prc = ldp_pgen_read_phased(pg, raw_v, 1, raw_row.data(), in_rec, nonmale_mask.data(), 1, &at);
                 if (prc == LDP_ERR_UNPHASED) {
-                  uint32_t cur = x_unphased.load();
-                  while ((raw_v < cur) && !x_unphased.compare_exchange_weak(cur, raw_v)) {
-                  }
+                  atomic_min(&x_unphased, raw_v);
                   continue;
                 }
                 if (prc) {
@@ -1435,18 +1399,15 @@ struct PruneJob {
         if (x_unphased.load() != UINT32_MAX) {
           die_unphased(x_unphased.load());
         }
-        if (ldp_load_genotypes(se, w0, cnt, rows.data(), s_rec, LDP_MEM_HOST, LDP_GENO_INVERSE) || ldp_set_maj_freqs(se, w0, cnt, mfs.data())) {
-          die(16, "\nError: %s\n", ldp_last_error(se));
-        }
+        must(se, ldp_load_genotypes(se, w0, cnt, rows.data(), s_rec, LDP_MEM_HOST, LDP_GENO_INVERSE));
+        must(se, ldp_set_maj_freqs(se, w0, cnt, mfs.data()));
       }
       const std::vector<uint64_t> pref_s = sub_preferred(ks);
       if (!pref_s.empty()) {
         ldp_set_preferred(se, pref_s.data());
       }
       std::vector<uint64_t> bm((ks.size() + 63) / 64 + 1, 0);
-      if (ldp_run(se, bm.data())) {
-        die(16, "\nError: %s\n", ldp_last_error(se));
-      }
+      must(se, ldp_run(se, bm.data()));
       scatter(bm, ks);
       ldp_destroy(se);
     }

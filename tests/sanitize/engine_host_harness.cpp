@@ -26,6 +26,36 @@ int main() {
     else if (mode == 1) rc = ldp_set_variants_vcor(e, m, chr.data(), bp.data(), 1000 + rng() % 100000, 1 + rng() % 500);
     else rc = ldp_set_variants_matrix(e, m);
     if (rc) { printf("plan rc %d: %s\n", rc, ldp_last_error(e)); return 1; }
+    // the passes over resident rows on an engine that has loaded nothing: random ranges (out of range and empty ones too) end in a return
+    // code before the first device call, whatever the plan owns
+    {
+      const uint32_t fc = P.founder_ct;
+      std::vector<uint32_t> c32a(fc), c32b(fc);
+      std::vector<uint64_t> c64(fc), weight(m + 8);
+      std::vector<uint8_t> flags(m + 8);
+      std::vector<double> ln_p(m + 8);
+      std::vector<ldp_king_counts_t> dense(static_cast<size_t>(8) * 8);
+      std::vector<ldp_king_hit> hits(16);
+      for (int t = 0; t < 24; ++t) {
+        const uint32_t first = rng() % (m + 4);
+        const uint32_t n = (t % 4 == 0) ? 0 : ((t % 4 == 1) ? rng() % 8 : rng() % (m + 4));
+        const uint32_t row_first = rng() % fc, col_first = rng() % fc;
+        uint64_t found = 0;
+        int rcs[5];
+        rcs[0] = ldp_sample_missing_counts(e, first, n, c32a.data());
+        rcs[1] = ldp_sample_het_counts(e, first, n, nullptr, (t & 1) ? weight.data() : nullptr, c32a.data(), c32b.data(), (t & 1) ? c64.data() : nullptr);
+        rcs[2] = ldp_king_counts_block(e, first, n, nullptr, row_first, 8, col_first, 8, dense.data(), 8);
+        // (the hit form of an empty range with pairs goes on to the device: kept to ranges that refuse, or to blocks without a pair)
+        rcs[3] = ldp_king_block_hits(e, first, n, nullptr, row_first, n ? 8 : 1, n ? col_first : row_first, n ? 8 : 1, 0.1, hits.data(), hits.size(), &found);
+        rcs[4] = ldp_hwe_ln_pvals(e, first, n, t & 1, ln_p.data(), flags.data());
+        for (int k = 0; k < 5; ++k) {
+          if ((rcs[k] != LDP_OK) && (rcs[k] != LDP_ERR_STATE) && (rcs[k] != LDP_ERR_INVALID) && (rcs[k] != LDP_ERR_UNSUPPORTED)) {
+            printf("resident pass %d on (%u, %u): rc %d: %s\n", k, first, n, rcs[k], ldp_last_error(e));
+            return 1;
+          }
+        }
+      }
+    }
     std::vector<uint32_t> lo(m); uint64_t cand = 0;
     ldp_get_band(e, lo.data(), &cand);
     uint32_t sct = 0; ldp_get_subcontigs(e, &sct, nullptr, 0);
