@@ -26,6 +26,19 @@ int ldp_debug_replay_pairs(ldp_engine* e, uint64_t n_true, const uint32_t* first
  * part of `out`).  LDP_ERR_STATE when no run has completed since the last load (the rows are cleared group by group as launches are
  * queued), LDP_ERR_INVALID when capacity < candidate pairs, LDP_ERR_UNSUPPORTED on a sharded engine.  Reads finished results only. */
 int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t* outside_band);
+/* What the host replay of the last ldp_run() READ: the predicate rows as the device compacted them (csrc/ldp_pred_csr.hip) into pinned host
+ * memory.  meta receives two words per local row j -- (first entry, entries) --, ent two words per entry in use -- (word index inside the
+ * row, bits; bit b of word w of row j: the pair (32 ((lo[j] >> 5) + w) + b, j)) --; a row's entries ascend by word index, the rows' runs
+ * lie in no particular order.  *n_rows: the rows (shard-local variants), *used: the entries in use (the device's count, capped by the
+ * capacity), *device_count: the non-zero words the device counted (one copy of the counter, after waiting for the engine's stream),
+ * *overflow: 1 when that exceeded *capacity (the entries in force, option "csr_capacity") -- the run then replayed the dense rows instead,
+ * and meta / ent are incomplete --, *overflow_runs: the runs of this engine that fell back so.  Any output pointer may be NULL; meta and
+ * ent both NULL only reports the counts.  Reads finished results only: no kernel is launched, nothing a run does changes.
+ * LDP_ERR_STATE when the last completed run returned no compacted rows -- no run since the last load, an inspection run
+ * (ldp_run_with_stats), an engine with "pred_csr" 0 --, LDP_ERR_INVALID when meta_capacity < rows or ent_capacity < entries in use (both in
+ * pairs of words), LDP_ERR_UNSUPPORTED on a sharded engine. */
+int ldp_debug_get_pred_csr(ldp_engine* e, uint32_t* meta, uint64_t meta_capacity, uint32_t* ent, uint64_t ent_capacity, uint32_t* n_rows, uint64_t* used,
+                           uint64_t* device_count, uint32_t* overflow, uint64_t* capacity, uint32_t* overflow_runs);
 /* Kernel-selection switches of ONE engine, for tests and measurements (the defaults are what production runs use).  The shipped
  * library reads NO environment variable (csrc/ldp_env.h): this call is the only way to switch anything, engine by engine; only the
  * measurement build (-DLDP_MEASURE, lib/libldprune_hip_measure.so, tools/) presets them from LDP_* variables.  name:
@@ -65,6 +78,10 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
  *   "wide_min_reach"  row-blocks a subcontig's band must reach to take the 8 x 8 tile plan of the wide-band kernel; 0 = always,
  *                     a huge value = never (before ldp_set_variants())
  *   "replay_steps"    k: ldp_debug_replay_pairs() walks every subcontig in k instalments, the way the streaming replay of a run advances
+ *   "replay_csr"      0/1/2: ldp_debug_replay_pairs() builds the CSR form of its dense rows with a plain host loop -- per row (first entry, entries),
+ *                     per non-zero word (word index inside the row, bits), ascending: the written specification of pred_compact_kernel's output
+ *                     -- and replays through the view a production run reads; 1 = the runs of the 64-row blocks ascend, 2 = they descend (the
+ *                     device's blocks land in the order of their atomic adds); 0 = the dense rows (default).  Other values: LDP_ERR_INVALID
  *   "decode_rows"     k: ldp_load_pgen_records*() decode in launches of k rows (LD chains cut everywhere)
  *   "decode_no_lds"   0/1: decoded rows are assembled in global memory (what rows beyond 128 KiB take) instead of LDS
  *   "x_rows"          k: ldp_r2_unphased_block_x*() work in chunks of k rows

@@ -122,7 +122,7 @@ CABI_SYMBOLS = [
     "ldp_king_counts_block", "ldp_king_block_hits", "ldp_debug_king_counts_block",
     "ldp_hwe_ln_pvals", "ldp_hwe_ln_pvals_counts", "ldp_hwe_ln_p_host", "ldp_debug_hwe_ln_pvals", "ldp_debug_hwe_ln_pvals_counts",
     "ldp_r2_phased_stats_block", "ldp_r2_phased_band_stats", "ldp_r2_phased_band_hits", "ldp_phased_ld", "ldp_debug_get_phased_filter",
-    "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass", "ldp_get_allele_counts",
+    "ldp_get_dosage_sums", "ldp_debug_get_cp_stats", "ldp_debug_get_count_pass", "ldp_get_allele_counts", "ldp_debug_get_pred_csr",
 ]
 
 
@@ -240,6 +240,7 @@ def lib():
     L.ldp_debug_set_variant_recs.argtypes = [vp, vp]
     L.ldp_debug_replay_pairs.argtypes = [vp, ctypes.c_uint64, u32p, u32p, u64p]
     L.ldp_debug_get_pred.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64, u64p]
+    L.ldp_debug_get_pred_csr.argtypes = [vp, u32p, ctypes.c_uint64, u32p, ctypes.c_uint64, u32p, u64p, u64p, u32p, u64p, u32p]
     L.ldp_debug_get_cp_stats.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, u32p, u32p]
     L.ldp_debug_get_count_pass.argtypes = [vp, u32p, u32p, u32p]
     L.ldp_map_rows.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp), u64p]
@@ -1086,6 +1087,21 @@ class LdPruneEngine:
         self._ck(self._L.ldp_debug_get_pred(self._h, _ptr(out, ctypes.c_uint8), cand, ctypes.byref(outside)))
         pred = out[:cand].astype(bool)
         return (pred, int(outside.value)) if with_outside else pred
+
+    def last_pred_csr(self):
+        """The compacted predicate rows the replay of the last run() read (ldp_debug_get_pred_csr): a dict with 'meta' ((rows, 2) uint32: first
+        entry, entries of every shard-local row), 'ent' ((used, 2) uint32: word index inside the row, bits), 'used', 'device_count' (the
+        device's counter), 'overflow' (the flag), 'capacity' and 'overflow_runs' (runs of this engine that fell back to the dense rows).
+        LdpError(LDP_ERR_STATE) when the last completed run returned no compacted rows."""
+        rows, flag, runs = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        used, counted, cap = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        tail = (ctypes.byref(rows), ctypes.byref(used), ctypes.byref(counted), ctypes.byref(flag), ctypes.byref(cap), ctypes.byref(runs))
+        self._ck(self._L.ldp_debug_get_pred_csr(self._h, None, 0, None, 0, *tail))
+        meta = np.zeros((max(rows.value, 1), 2), dtype=np.uint32)
+        ent = np.zeros((max(used.value, 1), 2), dtype=np.uint32)
+        self._ck(self._L.ldp_debug_get_pred_csr(self._h, _ptr(meta, ctypes.c_uint32), meta.shape[0], _ptr(ent, ctypes.c_uint32), ent.shape[0], *tail))
+        return {"meta": meta[:rows.value], "ent": ent[:used.value], "used": int(used.value), "device_count": int(counted.value),
+                "overflow": int(flag.value), "capacity": int(cap.value), "overflow_runs": int(runs.value)}
 
     def pair_stats(self, first, second):
         first, second = _u32(first), _u32(second)

@@ -1798,6 +1798,11 @@ int ldp_debug_set_option(ldp_engine* e, const char* name, double value) {
     e->opt.wide_sparse = (value != 0.0);
   } else if (n == "replay_steps") {
     e->opt.replay_steps = static_cast<uint32_t>(std::max(0.0, value));
+  } else if (n == "replay_csr") {
+    if ((value != 0.0) && (value != 1.0) && (value != 2.0)) {
+      return fail(e, LDP_ERR_INVALID, "replay_csr must be 0, 1 or 2");
+    }
+    e->opt.replay_csr = static_cast<uint32_t>(value);
   } else if (n == "decode_rows") {
     e->opt.decode_rows = static_cast<uint32_t>(std::max(0.0, value));
   } else if (n == "decode_no_lds") {
@@ -1856,7 +1861,11 @@ int ldp_debug_replay_pairs(ldp_engine* e, uint64_t n_true, const uint32_t* first
   }
   std::vector<uint32_t> R((static_cast<size_t>(e->local_ct) + 31) / 32 + 1, 0);
   uint64_t replay_pairs = 0;
-  replay(e, pred.data(), mf, R, &replay_pairs);
+  if (e->opt.replay_csr) {
+    replay_as_csr(e, pred.data(), e->opt.replay_csr, mf, R, &replay_pairs);
+  } else {
+    replay(e, pred.data(), mf, R, &replay_pairs);
+  }
   e->ctr.replay_pairs = replay_pairs;
   return finish_removed(e, R, removed);
 }

@@ -202,6 +202,7 @@ struct EngineOptions {
                                // the kernel its own rows call for, capped by the word (tile_route_kernel)
   // test hooks (ldp_debug_set_option only; 0 = off): results never depend on them
   uint32_t replay_steps = 0;   // "replay_steps" k: ldp_debug_replay_pairs() walks every subcontig in k instalments, as the streaming replay of a run does
+  uint32_t replay_csr = 0;     // "replay_csr" 1 / 2: ldp_debug_replay_pairs() replays through the CSR view of its rows (2: the 64-row blocks' runs in descending order)
   uint32_t decode_rows = 0;    // "decode_rows" k: record decode in launches of k rows (LD chains cut everywhere)
   bool decode_no_lds = false;  // "decode_no_lds" 1: decoded rows are assembled in global memory (what rows beyond 128 KiB take) instead of LDS
   uint32_t x_rows = 0;         // "x_rows" k: the chrX-weighted blocks in chunks of k rows
@@ -349,6 +350,7 @@ struct ldp_engine {
   // the count pass of the last load: {1 = codes_kernel / 0 = prepare_kernel, THREADS, ITERS} of its launch; THREADS 0 = none yet (ldp_debug_get_count_pass)
   uint32_t count_pass[3] = {0, 0, 0};
   bool pred_valid = false;     // a run has completed since the last load: d_pred holds its decisions (ldp_debug_get_pred)
+  bool pred_csr_valid = false; // ... and that run returned its rows as CSR (a production run of an engine with pred_csr): read with pred_valid (ldp_debug_get_pred_csr)
   uint32_t* h_pred = nullptr;  // pinned; allocated when a run needs the dense rows (inspection runs, engines without pred_csr, the overflow fallback)
   // the predicate rows as CSR (ldp_pred_csr.hip), written by the device straight into these pinned buffers; h_csr_flag[0] = overflow
   uint2* h_csr_meta = nullptr;
@@ -513,6 +515,7 @@ int resident_runs(ldp_engine* e, const char* who, uint32_t first_variant, uint32
 int begin_resident_read(ldp_engine* e);
 // ldp_engine_run.cpp: launches and replay
 void replay(ldp_engine* e, const uint32_t* pred, const double* mf, std::vector<uint32_t>& R, uint64_t* replay_pairs_out);
+void replay_as_csr(ldp_engine* e, const uint32_t* pred, uint32_t layout, const double* mf, std::vector<uint32_t>& R, uint64_t* replay_pairs_out);
 int finish_removed(ldp_engine* e, const std::vector<uint32_t>& R, uint64_t* removed);
 int prepare_mf(ldp_engine* e, std::vector<double>* scratch, const double** mf_out);
 void fill_pair_args(const ldp_engine* e, PairKernelArgs* out, bool with_early_exit);

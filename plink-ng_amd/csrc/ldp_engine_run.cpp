@@ -132,10 +132,9 @@ uint64_t replay_subcontig(const ldp_engine* e, uint32_t k, const PredView& pv, c
           if (fu == ne) {
             continue;
           }
-          uint32_t second = next_clear(R, first + 1, ne);
-          while ((second < ne) && (second < fu)) {
-            second = next_clear(R, second + 1, ne);
-          }
+          // the first live variant behind `first` that it has not been checked against (one word scan: stepping there one live variant
+          // at a time made a batch cost window^2 where few variants are removed)
+          uint32_t second = next_clear(R, std::max(first + 1, fu), ne);
           if (second >= ne) {
             first_unchecked[first] = ne;
             continue;
@@ -290,6 +289,35 @@ void replay_view(ldp_engine* e, const PredView& pred, const double* mf, std::vec
 
 void replay(ldp_engine* e, const uint32_t* pred, const double* mf, std::vector<uint32_t>& R, uint64_t* replay_pairs_out) {
   const PredView pv = {pred, nullptr, nullptr, 0};
+  replay_view(e, pv, mf, R, replay_pairs_out);
+}
+
+// option "replay_csr" (test hook): the CSR view of dense rows, built the way pred_compact_kernel's output is SPECIFIED -- per row its non-zero
+// words, ascending by word index; the rows of a block of 64 one behind the other -- and replayed through the branch a production run takes.
+// layout 1: the blocks' runs ascend; 2: they descend (on the device they land in whatever order the blocks' atomicAdds fall).
+void replay_as_csr(ldp_engine* e, const uint32_t* pred, uint32_t layout, const double* mf, std::vector<uint32_t>& R, uint64_t* replay_pairs_out) {
+  constexpr uint32_t kBlockRows = 64;
+  const uint32_t rows = e->local_ct;
+  const uint32_t blocks = (rows + kBlockRows - 1) / kBlockRows;
+  std::vector<uint2> meta(std::max<size_t>(rows, 1), make_uint2(0, 0));
+  std::vector<uint2> ent;
+  for (uint32_t q = 0; q < blocks; ++q) {
+    const uint32_t b = (layout == 2) ? (blocks - 1 - q) : q;
+    for (uint32_t j = b * kBlockRows; (j < rows) && (j < (b + 1) * kBlockRows); ++j) {
+      const uint32_t* row = pred + e->row_off[j];
+      const uint64_t nw = e->row_off[j + 1] - e->row_off[j];
+      const size_t at = ent.size();
+      for (uint64_t w = 0; w < nw; ++w) {
+        if (row[w]) {
+          ent.push_back(make_uint2(static_cast<uint32_t>(w), row[w]));
+        }
+      }
+      meta[j] = make_uint2(static_cast<uint32_t>(at), static_cast<uint32_t>(ent.size() - at));
+    }
+  }
+  const uint64_t used = ent.size();
+  ent.resize(std::max<size_t>(ent.size(), 1), make_uint2(0, 0));
+  const PredView pv = {nullptr, meta.data(), ent.data(), used};
   replay_view(e, pv, mf, R, replay_pairs_out);
 }
 
@@ -654,6 +682,7 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
   double replay_busy_ms = 0.0;
   unsigned long long h_counters[4] = {0, 0, 0, 0};
   bool tile_routed = false;  // some launch of this run gave its tiles a class each (launch_group)
+  bool ran_csr = false;      // the rows came back as CSR (a production run of an engine with pred_csr; an engine without rows has none to return)
   if (stats) {
     // Inspection run: one launch over every item, every pair's integers stored, no early termination.
     // Whatever the side streams hold is waited for and superseded.
@@ -806,6 +835,7 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
     // 3. ... and replays each group's subcontigs as soon as its predicate words are back.
     t_replay = now_ms();
     const bool csr = use_pred_csr(e);
+    ran_csr = csr || (e->opt.pred_csr && !e->local_ct);
     const PredView pview = csr ? PredView{nullptr, e->h_csr_meta, e->h_csr_ent, e->csr_capacity} : PredView{e->h_pred, nullptr, nullptr, 0};
     rc = replay_progressive(e, pview, mf, R, &replay_pairs, &replay_busy_ms);
     if (rc) {
@@ -920,6 +950,7 @@ int run_impl(ldp_engine* e, uint64_t* removed, ldp_pair_stats_t* stats, uint64_t
   e->ctr.ms_run_total = t_end - t_start;
   e->ctr.pair_kernel_launches = launches;
   e->pred_valid = true;  // every group's rows are complete in d_pred until the next load clears them
+  e->pred_csr_valid = ran_csr;
   return LDP_OK;
 }
 
@@ -990,6 +1021,60 @@ int ldp_debug_get_pred(ldp_engine* e, uint8_t* out, uint64_t capacity, uint64_t*
   }
   if (outside_band) {
     *outside_band = outside;
+  }
+  return LDP_OK;
+}
+
+int ldp_debug_get_pred_csr(ldp_engine* e, uint32_t* meta, uint64_t meta_capacity, uint32_t* ent, uint64_t ent_capacity, uint32_t* n_rows, uint64_t* used,
+                           uint64_t* device_count, uint32_t* overflow, uint64_t* capacity, uint32_t* overflow_runs) {
+  if (!e) {
+    return LDP_ERR_INVALID;
+  }
+  if (!e->planned || e->matrix_mode || e->band_r2_mode) {
+    return fail(e, LDP_ERR_STATE, "no prune plan (ldp_set_variants)");
+  }
+  if (e->world > 1) {
+    return fail(e, LDP_ERR_UNSUPPORTED, "ldp_debug_get_pred_csr: sharded engines are not supported");
+  }
+  if (!e->pred_valid || !e->pred_csr_valid) {
+    return fail(e, LDP_ERR_STATE, "the last completed run returned no compacted rows (no run since the last load, an inspection run, or option pred_csr 0)");
+  }
+  unsigned long long counted = 0;
+  if (e->d_csr_counter) {
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipMemcpy(&counted, e->d_csr_counter, sizeof(counted), hipMemcpyDeviceToHost));
+  }
+  const uint64_t in_use = std::min<uint64_t>(counted, e->csr_capacity);  // (an overflowed run: what the buffer holds)
+  if (n_rows) {
+    *n_rows = e->local_ct;
+  }
+  if (used) {
+    *used = in_use;
+  }
+  if (device_count) {
+    *device_count = counted;
+  }
+  if (overflow) {
+    *overflow = e->h_csr_flag ? e->h_csr_flag[0] : 0u;
+  }
+  if (capacity) {
+    *capacity = e->csr_capacity;
+  }
+  if (overflow_runs) {
+    *overflow_runs = e->ctr_csr_overflows;
+  }
+  if (!meta && !ent) {
+    return LDP_OK;  // (only the counts: what the caller sizes its buffers by)
+  }
+  if ((meta_capacity < e->local_ct) || (ent_capacity < in_use) || (e->local_ct && !meta) || (in_use && !ent)) {
+    return fail(e, LDP_ERR_INVALID, "buffer smaller than the rows / the entries in use");
+  }
+  if (e->local_ct) {
+    memcpy(meta, e->h_csr_meta, static_cast<size_t>(e->local_ct) * sizeof(uint2));
+  }
+  if (in_use) {
+    memcpy(ent, e->h_csr_ent, static_cast<size_t>(in_use) * sizeof(uint2));
   }
   return LDP_OK;
 }

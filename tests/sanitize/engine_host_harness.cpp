@@ -71,7 +71,20 @@ int main() {
         std::vector<uint32_t> f, s2;
         for (uint32_t j = 1; j < m; ++j) if (lo[j] < j && rng() % 3 == 0) { f.push_back(lo[j] + rng() % (j - lo[j])); s2.push_back(j); }
         std::vector<uint64_t> removed((m + 63) / 64 + 1);
-        ldp_debug_replay_pairs(e, f.size(), f.data(), s2.data(), removed.data());
+        const int drc = ldp_debug_replay_pairs(e, f.size(), f.data(), s2.data(), removed.data());
+        // ... and through the CSR view of the same rows (option "replay_csr": block runs ascending / descending), whole and in three
+        // instalments: the entries walked backwards, pred_word()'s search and the resume over them give the dense replay's words
+        for (int view = 1; (view <= 2) && !drc; ++view) {
+          for (int steps = 0; steps <= 3; steps += 3) {
+            std::vector<uint64_t> again(removed.size());
+            ldp_debug_set_option(e, "replay_csr", view);
+            ldp_debug_set_option(e, "replay_steps", steps);
+            const int rrc = ldp_debug_replay_pairs(e, f.size(), f.data(), s2.data(), again.data());
+            if (rrc || (again != removed)) { printf("iter %d: replay_csr %d, replay_steps %d: rc %d, removed words differ from the dense replay's\n", iter, view, steps, rrc); return 1; }
+          }
+        }
+        ldp_debug_set_option(e, "replay_csr", 0);
+        ldp_debug_set_option(e, "replay_steps", 0);
       }
     }
     ldp_destroy(e);

@@ -970,6 +970,13 @@ def test_predicate_rows_as_csr_dense_and_overflow_agree(gpu_pkg, order):
         got = eng.run()
         again = eng.run()
         c = eng.counters()
+        if options.get("pred_csr", 1):
+            # what the runs did with the compacted rows (ldp_debug_get_pred_csr): the default engine never fell back, the one with room for 16
+            # entries raised the flag and fell back to the dense rows once per run (`pred_true` counts bits; this counts words)
+            csr = eng.last_pred_csr()
+            fell_back = "csr_capacity" in options
+            assert csr["overflow"] == (1 if fell_back else 0) and csr["overflow_runs"] == (2 if fell_back else 0), (options, csr["overflow"], csr["overflow_runs"])
+            assert csr["device_count"] > 16 and csr["capacity"] == (16 if fell_back else csr["capacity"]) and (fell_back or csr["used"] == csr["device_count"])
         eng.close()
         assert np.array_equal(got, want), options
         assert np.array_equal(again, want), options
