@@ -517,6 +517,56 @@ struct XWeighted {
 
 int chrom_code(const std::string& name_in);
 bool chrom_listed(const std::vector<std::string>& terms, const std::string& name);
+// The variant-table filters -- chromosome out by --chr / --not-chr / --autosome, --max-alleles, --snps-only, then --extract, then --exclude --
+// for every stage of load_inputs(), which builds one (reading the ID files) per call.
+struct ChromFacts {
+  bool out;   // by --chr / --not-chr / --autosome
+  bool zero;  // chromosome 0
+  int cls;    // chrom_class()
+  int code;   // chrom_code()
+};
+struct VariantFilter {
+  const Args& A;
+  const Variants& V;
+  const bool by_chrom;  // --chr / --not-chr / --autosome given
+  VariantFilter(const Args& args, const Variants& variants);
+  // a chromosome name's facts, computed when the name is first asked about
+  const ChromFacts& chrom(const std::string& name);
+  enum Verdict { kByTable, kByExtract, kByExclude, kPass };  // what drops raw variant v, in the order the reference's log counts survivors
+  bool table_passes(uint32_t v) { return (!chrom(V.chrom[v]).out) && (allele_ct_for_filter(V, v) <= A.max_alleles) && !(A.snps_only && V.not_snp[v]); }
+  Verdict verdict(uint32_t v) {
+    return (!table_passes(v)) ? kByTable
+           : (((!A.extract_files.empty()) && !extract_ids_.count(V.id[v])) ? kByExtract : (((!A.exclude_files.empty()) && exclude_ids_.count(V.id[v])) ? kByExclude : kPass));
+  }
+  bool passes(uint32_t v) { return verdict(v) == kPass; }
+  // The raw variants in file order: on_chrom(name, facts) when a chromosome name is first met, before any of its variants is tested -- so a
+  // refusal about a chromosome fires even where none of its variants passes, and after a refusal about a variant of an earlier chromosome --,
+  // on_variant(v, facts) for every variant that passes.
+  template <class OnChrom, class OnVariant>
+  void walk(OnChrom on_chrom, OnVariant on_variant) {
+    std::unordered_set<const ChromFacts*> met;
+    const ChromFacts* cur = nullptr;
+    const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
+    for (uint32_t v = 0; v < raw_variant_ct; ++v) {
+      const ChromFacts& c = chrom(V.chrom[v]);
+      if (&c != cur) {
+        cur = &c;
+        if (met.insert(cur).second) {
+          on_chrom(V.chrom[v], c);
+        }
+      }
+      if (passes(v)) {
+        on_variant(v, c);
+      }
+    }
+  }
+
+ private:
+  std::unordered_set<std::string> extract_ids_, exclude_ids_;
+  std::unordered_map<std::string, ChromFacts> chroms_;
+  const std::string* last_name_ = nullptr;  // (the table's chromosomes come in runs: the name and facts last asked about)
+  const ChromFacts* last_ = nullptr;
+};
 // what --clump needs to know about sex chromosomes (ClumpReports :8150-8215, :8460-8482)
 struct ClumpSex {
   const std::vector<uint8_t>* vcls = nullptr;  // per included variant: 3 chrX, 4 chrY
@@ -682,8 +732,7 @@ struct ReportCounts {
 };
 // the variants the reports list; refuses (exit 63) what the reports do not cover: chrX / chrY / MT, dosage tracks, a phenotype for .smiss, --geno-counts
 // with a variant that has several ALT alleles
-void reports_list_variants(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids,
-                           std::vector<uint32_t>* listed);
+void reports_list_variants(Session& S, VariantFilter& filter, std::vector<uint32_t>* listed);
 // the founders' allele counts of a listed variant with several ALT alleles, from the reader's allele pairs (ldp_pgen_read_alleles): the host
 // pass's source, and the device pass's for rows the host built
 void reports_count_alleles_host(const Session& S, uint32_t raw_variant, std::vector<uint8_t>* lo, std::vector<uint8_t>* hi, std::vector<uint32_t>* counts);

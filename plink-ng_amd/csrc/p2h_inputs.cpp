@@ -1,6 +1,8 @@
 // p2h_inputs.cpp -- plink2-hip: chromosome / sample filters and load_inputs(): everything the commands share (one translation unit of the front-end; plink2_hip_cli.cpp has the overview)
 #include "p2h_cli.h"
 
+#include <optional>
+
 namespace p2h {
 
 // --chr / --not-chr / --autosome: a chromosome's numeric code (1..22, X 23, Y 24, XY 25, MT 26, 0; -1 for other names)
@@ -325,6 +327,80 @@ const char* device_filter_refusal(const Args& A, bool has_dosage, uint32_t kept_
   return nullptr;
 }
 
+// --extract / --exclude by ID (TokenExtractExclude, plink2_filter.cc:367: every variant carrying a listed ID, unknown IDs ignored)
+VariantFilter::VariantFilter(const Args& args, const Variants& variants) : A(args), V(variants), by_chrom((!args.chr_keep.empty()) || (!args.chr_drop.empty()) || args.autosome) {
+  for (const std::string& fn : A.extract_files) {
+    for (std::string& t : tokens_of_file(fn)) {
+      extract_ids_.insert(std::move(t));
+    }
+  }
+  for (const std::string& fn : A.exclude_files) {
+    for (std::string& t : tokens_of_file(fn)) {
+      exclude_ids_.insert(std::move(t));
+    }
+  }
+}
+
+const ChromFacts& VariantFilter::chrom(const std::string& name) {
+  if (last_ && (*last_name_ == name)) {
+    return *last_;
+  }
+  auto it = chroms_.find(name);
+  if (it == chroms_.end()) {
+    ChromFacts c;
+    c.code = chrom_code(name);
+    c.out = by_chrom && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, name)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, name)) ||
+                         (A.autosome && !((c.code >= 1) && (c.code <= 22))));
+    c.cls = chrom_class(name, A.allow_extra_chr, &c.zero);
+    it = chroms_.emplace(name, c).first;
+  }
+  last_name_ = &it->first;
+  last_ = &it->second;
+  return *last_;
+}
+
+// One bit pair (01) per founder (m_f) / kept sample (m_s), 32 samples per word, and how many there are of each: as is_founder and sample_kept
+// stand when it is asked for (--mind and --make-founders change them between the stages)
+struct SampleMasks {
+  std::vector<uint64_t> m_f, m_s;
+  uint32_t kept_samples = 0, founders = 0;
+};
+static SampleMasks sample_masks(const Session& S) {
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  SampleMasks M;
+  M.m_f.assign((static_cast<size_t>(raw_sample_ct) + 31) / 32, 0);
+  M.m_s = M.m_f;
+  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+    const uint64_t bit = 1ull << (2 * (sx & 31));
+    if (S.sample_kept.empty() || S.sample_kept[sx]) {
+      M.m_s[sx >> 5] |= bit;
+      ++M.kept_samples;
+    }
+    if (S.is_founder[sx]) {
+      M.m_f[sx >> 5] |= bit;
+      ++M.founders;
+    }
+  }
+  return M;
+}
+
+static uint32_t host_pass_threads() {
+  return std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+}
+
+// the autosomal variants of the final list (chromosome 0 counts as one, CountNonAutosomalVariants plink2_common.cc:3334); returns how many are not
+static uint32_t autosomal_of_final_list(const Session& S, std::vector<uint32_t>* todo) {
+  uint32_t non_autosomal = 0;
+  for (size_t k = 0; k < S.inc.size(); ++k) {
+    if (S.vcls[k] >= 3) {
+      ++non_autosomal;
+    } else {
+      todo->push_back(S.inc[k]);
+    }
+  }
+  return non_autosomal;
+}
+
 // ---- --mind (LoadSampleMissingCts plink2_data.cc:10846-10990, MindFilter plink2_filter.cc:3329-3383)
 // per-sample missing hardcalls of rows: cts[sample of the file] += 1 for every kept sample (m_s: one 01 bit pair per kept sample) whose call is missing
 static void count_sample_missing(const uint8_t* rows, uint64_t stride, uint32_t n_rows, bool bed, uint32_t raw_sample_ct, const std::vector<uint64_t>& m_s, uint32_t* cts) {
@@ -347,7 +423,37 @@ static void count_sample_missing(const uint8_t* rows, uint64_t stride, uint32_t 
   }
 }
 
-uint32_t mind_decide(const Session& S, const std::vector<uint32_t>& missing_cts, std::vector<uint8_t>* removed) {
+// ... on the threads of a pass over the rows: one array per thread, summed at the end
+struct SampleMissingParts {
+  std::vector<std::vector<uint32_t>> part;
+  SampleMissingParts(uint32_t nthreads, size_t mask_words) : part(nthreads, std::vector<uint32_t>(32 * mask_words, 0)) {}
+  std::vector<uint32_t> sum(uint32_t raw_sample_ct) const {
+    std::vector<uint32_t> cts(raw_sample_ct, 0);
+    for (const std::vector<uint32_t>& p : part) {
+      for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
+        cts[sx] += p[sx];
+      }
+    }
+    return cts;
+  }
+};
+// per sample of the file: the missing hardcalls of the kept samples over the variants `todo`
+static std::vector<uint32_t> sample_missing_over(const Session& S, const std::vector<uint32_t>& todo, const std::vector<uint64_t>& m_s) {
+  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  int storage_mode = 0;
+  ldp_pgen_info(S.pg, nullptr, nullptr, &storage_mode, nullptr, nullptr);
+  const bool bed = (storage_mode == 0x01);
+  uint64_t rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
+  const uint8_t* direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(S.pg, &rec_bytes));  // NULL for variable-width
+  const uint32_t nthreads = host_pass_threads();
+  SampleMissingParts parts(nthreads, m_s.size());
+  for_each_row_run(S.pg, S.gpath, direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t) {
+    count_sample_missing(rows, rec_bytes, n, bed, raw_sample_ct, m_s, parts.part[t].data());
+  });
+  return parts.sum(raw_sample_ct);
+}
+
+uint32_t mind_decide(const Session& S,const std::vector<uint32_t>& missing_cts, std::vector<uint8_t>* removed) {
   const Args& A = S.A;
   const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
   // a sample goes when it misses more than (int32_t)(variant_ct * (thresh * (1 + 2^-44))) calls (MindFilter :3340-3342; no chrY here)
@@ -412,73 +518,44 @@ void mind_apply(Session& S, const std::vector<uint8_t>& removed) {
 //   * the decision left to run_prune() (S.mind_device), which reads the counts off the resident image;
 //   * the host pass: a multi-threaded pass over the rows like the one --geno has -- fixed-width rows where they lie, variable-width records through
 //     ldp_pgen_read, .bed codes -- that counts the missing hardcalls of every kept sample (a dosage track changes no hardcall), then the decision.
-static void sample_filter_mind(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+static void sample_filter_mind(Session& S, VariantFilter& filter) {
   const Args& A = S.A;
   const Variants& V = S.V;
-  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
-  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
-  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome
   std::vector<uint32_t> todo;
   bool any_x_mt = false, any_multiallelic = false;
-  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
-    auto it = chr_state.find(V.chrom[v]);
-    if (it == chr_state.end()) {
-      const std::string& cur = V.chrom[v];
-      const int code = chrom_code(cur);
-      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                                       (A.autosome && !((code >= 1) && (code <= 22))));
-      bool zero = false;
-      const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
-      if (!out) {
-        if (cls == 2) {
+  filter.walk(
+      [&](const std::string& cur, const ChromFacts& c) {
+        if (c.out) {
+          return;
+        }
+        if (c.cls == 2) {
           die(6, "Error: Invalid chromosome code '%s'. (Use --allow-extra-chr to force it to be accepted.)\n", cur.c_str());
         }
-        if (cls == 4) {
+        if (c.cls == 4) {
           // (the reference counts chrY over the males only and gives the others a smaller denominator, MindFilter :3341-3355: not built)
           die(63, "Error: --mind with chrY variants ('%s') is not supported by plink2-hip: filter them out (--autosome, --not-chr y) or pre-filter with plink2.\n", cur.c_str());
         }
-        any_x_mt = any_x_mt || (cls == 3) || (cls == 5);
-      }
-      it = chr_state.emplace(cur, static_cast<uint8_t>(out)).first;
-    }
-    if (it->second || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
-      continue;
-    }
-    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
-      continue;
-    }
-    any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
-    todo.push_back(v);
-  }
+        any_x_mt = any_x_mt || (c.cls == 3) || (c.cls == 5);
+      },
+      [&](uint32_t v, const ChromFacts&) {
+        any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
+        todo.push_back(v);
+      });
   S.mind_variant_ct = static_cast<uint32_t>(todo.size());
   if (S.mind_decided) {
     mind_apply(S, S.mind_removed);
-    uint32_t kept = 0, founders = 0;
-    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-      kept += S.sample_kept[sx];
-      founders += S.is_founder[sx];
-    }
+  }
+  const SampleMasks M = sample_masks(S);
+  if (S.mind_decided) {
     g_log_mute = false;
-    logprintf("--mind: %u sample%s remaining (%u founder%s); the rows are loaded again without the removed samples.\n", kept, (kept == 1) ? "" : "s", founders,
-              (founders == 1) ? "" : "s");
+    logprintf("--mind: %u sample%s remaining (%u founder%s); the rows are loaded again without the removed samples.\n", M.kept_samples, (M.kept_samples == 1) ? "" : "s", M.founders,
+              (M.founders == 1) ? "" : "s");
     g_log_mute = true;
     return;
   }
-  int storage_mode = 0;
-  ldp_pgen_info(S.pg, nullptr, nullptr, &storage_mode, nullptr, nullptr);
-  uint32_t kept_samples = 0, founders = 0;
-  const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
-  std::vector<uint64_t> m_s(words, 0);
-  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-    if (S.sample_kept.empty() || S.sample_kept[sx]) {
-      m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
-      ++kept_samples;
-    }
-    founders += S.is_founder[sx];
-  }
   // from the resident image where the variant filters may come from the device's records, and where in addition the image's rows ARE the
   // hardcalls of the variants counted and its columns the final founders
-  const char* reason = device_filter_refusal(A, ldp_pgen_has_dosage(S.pg) != 0, kept_samples, founders);
+  const char* reason = device_filter_refusal(A, ldp_pgen_has_dosage(S.pg) != 0, M.kept_samples, M.founders);
   if (!reason) {
     reason = A.dry_run ? "--dry-run"
              : ((A.make_founders && !A.make_founders_first) ? "--make-founders runs after --mind, on the samples it leaves"
@@ -493,20 +570,7 @@ static void sample_filter_mind(Session& S, bool chr_filter, const std::unordered
     return;
   }
   const double t0 = now_s();
-  const bool bed = (storage_mode == 0x01);
-  uint64_t rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
-  const uint8_t* direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(S.pg, &rec_bytes));  // NULL for variable-width
-  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-  std::vector<std::vector<uint32_t>> part(nthreads, std::vector<uint32_t>(32 * words, 0));  // (per thread; summed below)
-  for_each_row_run(S.pg, S.gpath, direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t) {
-    count_sample_missing(rows, rec_bytes, n, bed, raw_sample_ct, m_s, part[t].data());
-  });
-  std::vector<uint32_t> missing_cts(raw_sample_ct, 0);
-  for (const std::vector<uint32_t>& p : part) {
-    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-      missing_cts[sx] += p[sx];
-    }
-  }
+  const std::vector<uint32_t> missing_cts = sample_missing_over(S, todo, M.m_s);
   std::vector<uint8_t> removed;
   if (mind_decide(S, missing_cts, &removed)) {
     mind_apply(S, removed);
@@ -519,27 +583,17 @@ static void sample_filter_mind(Session& S, bool chr_filter, const std::unordered
 // The reports' stage of load_inputs(): what they list, then either the decision that run_prune() writes them from the engine's records
 // (S.report_device: the same conditions as for the count filters, device_filter_refusal) or the host's pass -- count_rows over a founder mask
 // and a kept-sample mask, the per-sample pass --mind has, ldp_pgen_read_alleles for a variant with several ALT alleles -- and the writer.
-static void reports_stage(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+static void reports_stage(Session& S, VariantFilter& filter) {
   const Args& A = S.A;
   const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
-  reports_list_variants(S, chr_filter, extract_ids, exclude_ids, &S.report_variants);
+  reports_list_variants(S, filter, &S.report_variants);
   const std::vector<uint32_t>& todo = S.report_variants;
   if (todo.empty()) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
     die(13, "Error: No variants remaining after main filters.\n");
   }
-  const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
-  std::vector<uint64_t> m_f(words, 0), m_s(words, 0);
-  uint32_t kept_samples = 0, founders = 0;
-  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-    if (S.sample_kept.empty() || S.sample_kept[sx]) {
-      m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
-      ++kept_samples;
-    }
-    if (S.is_founder[sx]) {
-      m_f[sx >> 5] |= 1ull << (2 * (sx & 31));
-      ++founders;
-    }
-  }
+  const SampleMasks M = sample_masks(S);
+  const std::vector<uint64_t>&m_f = M.m_f, &m_s = M.m_s;
+  const uint32_t kept_samples = M.kept_samples, founders = M.founders;
   if (A.rep_freq && A.rep_freq_counts && (kept_samples != founders) && !A.ac_founders) {  // plink2.cc:2102-2105
     die(7, "Error: --mac/--max-mac/\"--freq counts\" specified, but with neither\n--ac-founders nor --nonfounders; and nonfounders are present.\n");
   }
@@ -558,22 +612,19 @@ static void reports_stage(Session& S, bool chr_filter, const std::unordered_set<
   }
   S.report_host_reason = reason;
   const double t0 = now_s();
-  int storage_mode = 0;
-  ldp_pgen_info(S.pg, nullptr, nullptr, &storage_mode, nullptr, nullptr);
-  const bool bed = (storage_mode == 0x01);
-  uint64_t rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
-  const uint8_t* direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(S.pg, &rec_bytes));  // NULL for variable-width
-  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  const bool bed = (S.storage_mode == 0x01);
+  const uint64_t rec_bytes = S.rec_bytes;
+  const uint32_t nthreads = host_pass_threads();
   const bool two_sets = (kept_samples != founders) && A.rep_gcount;  // (--geno-counts counts every kept sample, --freq the founders)
   std::vector<RowCounts> fc(todo.size()), sc(two_sets ? todo.size() : 0);
-  std::vector<std::vector<uint32_t>> part(A.rep_smiss() ? nthreads : 0, std::vector<uint32_t>(32 * words, 0));  // (per thread; summed below)
-  for_each_row_run(S.pg, S.gpath, direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t q) {
+  SampleMissingParts parts(A.rep_smiss() ? nthreads : 0, m_s.size());
+  for_each_row_run(S.pg, S.gpath, S.direct_rows, rec_bytes, todo, nthreads, [&](uint32_t t, const uint8_t* rows, uint32_t n, size_t q) {
     count_rows(rows, rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &fc[q]);
     if (two_sets) {
       count_rows(rows, rec_bytes, n, bed, raw_sample_ct, m_s, m_s, &sc[q]);
     }
-    if (!part.empty()) {
-      count_sample_missing(rows, rec_bytes, n, bed, raw_sample_ct, m_s, part[t].data());
+    if (!parts.part.empty()) {
+      count_sample_missing(rows, rec_bytes, n, bed, raw_sample_ct, m_s, parts.part[t].data());
     }
   });
   ReportCounts C;
@@ -607,12 +658,7 @@ static void reports_stage(Session& S, bool chr_filter, const std::unordered_set<
       }
     }
   }
-  C.sample_missing.assign(raw_sample_ct, 0);
-  for (const std::vector<uint32_t>& p : part) {
-    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-      C.sample_missing[sx] += p[sx];
-    }
-  }
+  C.sample_missing = parts.sum(raw_sample_ct);
   const bool muted = g_log_mute;  // (a run that --mind started over logs nothing twice; these lines are this load's own)
   g_log_mute = false;
   write_reports(S, C);
@@ -622,56 +668,48 @@ static void reports_stage(Session& S, bool chr_filter, const std::unordered_set<
   }
 }
 
-// The --het stage of load_inputs(): what is refused, then where the sums come from -- the resident image after the filters (S.het_device: the
-// conditions of the count filters, device_filter_refusal, and rows that ARE the hardcalls of autosomal biallelic variants), or het_host_pass().
-static void het_stage(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+// What het_stage and king_stage ask about the variants the table filters leave, and their refusal of chromosome 0 beside a command that strips
+// it (the reference counts unplaced variants as autosomal; the prune and the windowed tables strip them from the one list kept here).
+// command / alone: "--het" / "--het", "--make-king-table" / "it"
+struct ImageRowScan {
+  bool any_non_autosomal = false, any_multiallelic = false;
+};
+static ImageRowScan scan_for_image_pass(const Session& S, VariantFilter& filter, const char* command, const char* alone) {
   const Args& A = S.A;
   const Variants& V = S.V;
-  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
-  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
+  ImageRowScan scan;
+  filter.walk([](const std::string&, const ChromFacts&) {},
+              [&](uint32_t v, const ChromFacts& c) {
+                if (c.zero && (A.have_prune || (A.r2_table && !A.r2_inter))) {
+                  die(63, "Error: %s beside %s with chromosome 0 variants ('%s') is not supported by plink2-hip: run %s on its own, or filter them out (--not-chr 0).\n", command,
+                      A.have_prune ? "the prune" : "a windowed r^2 command", V.id[v].c_str(), alone);
+                }
+                scan.any_non_autosomal = scan.any_non_autosomal || (c.cls >= 3);
+                scan.any_multiallelic = scan.any_multiallelic || (V.alt_ct[v] > 1);
+              });
+  return scan;
+}
+// ... and the end of their reasons for the host's pass; too_many_founders: the command's own wording of it
+static const char* image_pass_refusal(uint32_t founders, const char* too_many_founders, const ImageRowScan& scan) {
+  return (founders < 2) ? "fewer than two founders (no engine)"
+         : ((founders > ldp_matrix_pipe_max_founders()) ? too_many_founders
+         : (scan.any_non_autosomal ? "chrX / chrY / MT variants (their rows are built for engines of their own)"
+         : (scan.any_multiallelic ? "multiallelic variants (their rows are collapsed on the way into the image)" : nullptr)));
+}
+
+// The --het stage of load_inputs(): what is refused, then where the sums come from -- the resident image after the filters (S.het_device: the
+// conditions of the count filters, device_filter_refusal, and rows that ARE the hardcalls of autosomal biallelic variants), or het_host_pass().
+static void het_stage(Session& S, VariantFilter& filter) {
+  const Args& A = S.A;
   if (ldp_pgen_has_dosage(S.pg)) {
     // (the reference takes the allele frequencies from the dosages where a record has them, plink2_data.cc:2421-2443)
     die(63, "Error: %s holds dosage data, which --het of plink2-hip does not read.  Use plink2 --make-pgen erase-dosage first.\n", S.gpath.c_str());
   }
-  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chromosome 0, 3 = chrX / chrY / MT
-  bool any_non_autosomal = false, any_multiallelic = false;
-  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
-    auto it = chr_state.find(V.chrom[v]);
-    if (it == chr_state.end()) {
-      const std::string& cur = V.chrom[v];
-      const int code = chrom_code(cur);
-      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                                       (A.autosome && !((code >= 1) && (code <= 22))));
-      bool zero = false;
-      const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
-      it = chr_state.emplace(cur, static_cast<uint8_t>(out ? 1 : (zero ? 2 : ((cls >= 3) ? 3 : 0)))).first;
-    }
-    if ((it->second == 1) || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
-      continue;
-    }
-    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
-      continue;
-    }
-    if ((it->second == 2) && (A.have_prune || (A.r2_table && !A.r2_inter))) {
-      // (the reference's --het counts unplaced variants as autosomal; the prune and the windowed tables strip them from the one list kept here)
-      die(63, "Error: --het beside %s with chromosome 0 variants ('%s') is not supported by plink2-hip: run --het on its own, or filter them out (--not-chr 0).\n",
-          A.have_prune ? "the prune" : "a windowed r^2 command", V.id[v].c_str());
-    }
-    any_non_autosomal = any_non_autosomal || (it->second == 3);
-    any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
-  }
-  uint32_t kept_samples = 0, founders = 0;
-  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-    kept_samples += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
-    founders += S.is_founder[sx];
-  }
-  const char* reason = device_filter_refusal(A, false, kept_samples, founders);
+  const ImageRowScan scan = scan_for_image_pass(S, filter, "--het", "--het");
+  const SampleMasks M = sample_masks(S);
+  const char* reason = device_filter_refusal(A, false, M.kept_samples, M.founders);
   if (!reason) {
-    reason = A.dry_run ? "--dry-run"
-             : ((founders < 2) ? "fewer than two founders (no engine)"
-             : ((founders > ldp_matrix_pipe_max_founders()) ? "more founders than the resident 2-bit image takes (the per-sample sums are read off it)"
-             : (any_non_autosomal ? "chrX / chrY / MT variants (their rows are built for engines of their own)"
-             : (any_multiallelic ? "multiallelic variants (their rows are collapsed on the way into the image)" : nullptr))));
+    reason = A.dry_run ? "--dry-run" : image_pass_refusal(M.founders, "more founders than the resident 2-bit image takes (the per-sample sums are read off it)", scan);
   }
   if (A.dry_run) {
     logprintf("dry-run: --het: %s%s\n", reason ? "host pass: " : "from the resident image", reason ? reason : "");
@@ -685,31 +723,16 @@ void het_host_pass(Session& S) {
   const Variants& V = S.V;
   const double t0 = now_s();
   const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
-  std::vector<uint32_t> todo;  // the autosomal variants of the final list (chromosome 0 counts as one, CountNonAutosomalVariants plink2_common.cc:3334)
-  uint32_t non_autosomal = 0;
-  for (size_t k = 0; k < S.inc.size(); ++k) {
-    if (S.vcls[k] >= 3) {
-      ++non_autosomal;
-    } else {
-      todo.push_back(S.inc[k]);
-    }
-  }
+  std::vector<uint32_t> todo;
+  const uint32_t non_autosomal = autosomal_of_final_list(S, &todo);
   het_preamble(S, static_cast<uint32_t>(todo.size()), non_autosomal);
-  const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
-  std::vector<uint64_t> m_f(words, 0), m_s(words, 0);
-  uint32_t kept_samples = 0;
-  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-    if (S.sample_kept.empty() || S.sample_kept[sx]) {
-      m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
-      ++kept_samples;
-    }
-    if (S.is_founder[sx]) {
-      m_f[sx >> 5] |= 1ull << (2 * (sx & 31));
-    }
-  }
+  const SampleMasks M = sample_masks(S);
+  const std::vector<uint64_t>&m_f = M.m_f, &m_s = M.m_s;
+  const size_t words = m_s.size();
+  const uint32_t kept_samples = M.kept_samples;
   const bool bed = (S.storage_mode == 0x01);
   const uint64_t rec_bytes = S.rec_bytes;
-  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  const uint32_t nthreads = host_pass_threads();
   // first pass: the founders' allele counts, hence every variant's expected heterozygosity and the plan of the integer sums
   std::vector<RowCounts> fc(todo.size());
   for_each_row_run(S.pg, S.gpath, S.direct_rows, rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
@@ -807,53 +830,17 @@ void het_host_pass(Session& S) {
 // The --make-king-table stage of load_inputs(), het_stage's neighbour: where the pair counts come from -- the resident image after the filters
 // (S.king_device: the conditions of het_device), or king_host_pass().  The table is made of hardcalls, so a dosage file is no refusal: it
 // takes the host's pass.
-static void king_stage(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids) {
+static void king_stage(Session& S, VariantFilter& filter) {
   const Args& A = S.A;
-  const Variants& V = S.V;
-  const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
-  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
-  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chromosome 0, 3 = chrX / chrY / MT
-  bool any_non_autosomal = false, any_multiallelic = false;
-  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
-    auto it = chr_state.find(V.chrom[v]);
-    if (it == chr_state.end()) {
-      const std::string& cur = V.chrom[v];
-      const int code = chrom_code(cur);
-      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                                       (A.autosome && !((code >= 1) && (code <= 22))));
-      bool zero = false;
-      const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
-      it = chr_state.emplace(cur, static_cast<uint8_t>(out ? 1 : (zero ? 2 : ((cls >= 3) ? 3 : 0)))).first;
-    }
-    if ((it->second == 1) || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
-      continue;
-    }
-    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
-      continue;
-    }
-    if ((it->second == 2) && (A.have_prune || (A.r2_table && !A.r2_inter))) {
-      // (the reference's table counts unplaced variants as autosomal; the prune and the windowed tables strip them from the one list kept here)
-      die(63, "Error: --make-king-table beside %s with chromosome 0 variants ('%s') is not supported by plink2-hip: run it on its own, or filter them out (--not-chr 0).\n",
-          A.have_prune ? "the prune" : "a windowed r^2 command", V.id[v].c_str());
-    }
-    any_non_autosomal = any_non_autosomal || (it->second == 3);
-    any_multiallelic = any_multiallelic || (V.alt_ct[v] > 1);
-  }
-  uint32_t kept_samples = 0, founders = 0;
-  for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-    kept_samples += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
-    founders += S.is_founder[sx];
-  }
-  const char* reason = device_filter_refusal(A, false, founders, founders);
+  const ImageRowScan scan = scan_for_image_pass(S, filter, "--make-king-table", "it");
+  const SampleMasks M = sample_masks(S);
+  const char* reason = device_filter_refusal(A, false, M.founders, M.founders);
   if (!reason) {
-    reason = (kept_samples != founders) ? "non-founders among the kept samples (the table lists them, the device's rows hold founders only)"
+    reason = (M.kept_samples != M.founders) ? "non-founders among the kept samples (the table lists them, the device's rows hold founders only)"
              : (ldp_pgen_has_dosage(S.pg) ? "the file has dosage tracks" : nullptr);
   }
   if (!reason) {
-    reason = (founders < 2) ? "fewer than two founders (no engine)"
-             : ((founders > ldp_matrix_pipe_max_founders()) ? "more founders than the resident 2-bit image takes (the pair counts are read off it)"
-             : (any_non_autosomal ? "chrX / chrY / MT variants (their rows are built for engines of their own)"
-             : (any_multiallelic ? "multiallelic variants (their rows are collapsed on the way into the image)" : nullptr)));
+    reason = image_pass_refusal(M.founders, "more founders than the resident 2-bit image takes (the pair counts are read off it)", scan);
   }
   if (A.dry_run) {
     char num[40];
@@ -869,15 +856,8 @@ void king_host_pass(Session& S) {
   const Args& A = S.A;
   const double t0 = now_s();
   const uint32_t raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
-  std::vector<uint32_t> todo;  // the autosomal variants of the final list (chromosome 0 counts as one, CountNonAutosomalVariants plink2_common.cc:3334)
-  uint32_t non_autosomal = 0;
-  for (size_t k = 0; k < S.inc.size(); ++k) {
-    if (S.vcls[k] >= 3) {
-      ++non_autosomal;
-    } else {
-      todo.push_back(S.inc[k]);
-    }
-  }
+  std::vector<uint32_t> todo;
+  const uint32_t non_autosomal = autosomal_of_final_list(S, &todo);
   std::vector<uint32_t> kept;  // sample of the file per kept sample
   for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
     if (S.sample_kept.empty() || S.sample_kept[sx]) {
@@ -891,7 +871,7 @@ void king_host_pass(Session& S) {
   std::vector<uint64_t> het(static_cast<size_t>(sample_ct) * words, 0), hom(het.size(), 0), alt(het.size(), 0);
   const bool bed = (S.storage_mode == 0x01);
   const uint64_t rec_bytes = S.rec_bytes;
-  const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  const uint32_t nthreads = host_pass_threads();
   for_each_row_run(S.pg, S.gpath, S.direct_rows, rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
     for (uint32_t r = 0; r < n; ++r) {
       const uint8_t* row = rows + static_cast<uint64_t>(r) * rec_bytes;
@@ -924,11 +904,414 @@ void king_host_pass(Session& S) {
   }
 }
 
+// --make-founders (MakeFounders, plink2_filter.cc:4372-4443): a non-founder with a parent (both, with 'require-2-missing') that
+// is not among the samples in play becomes a founder; 'first' applies it before --keep / --remove, else after them
+static void make_founders(Session& S, const std::vector<std::pair<std::string, std::string>>& parent_keys, const std::vector<uint8_t>* included) {
+  const Args& A = S.A;
+  const std::vector<std::string>& sample_keys = S.sample_keys;
+  std::unordered_set<std::string> present;
+  bool any_nonfounder = false;
+  for (size_t sx = 0; sx < sample_keys.size(); ++sx) {
+    if ((!included) || (*included)[sx]) {
+      present.insert(sample_keys[sx]);
+      any_nonfounder = any_nonfounder || !S.is_founder[sx];
+    }
+  }
+  if (!any_nonfounder) {
+    logprintf("Note: Skipping --make-founders since there are no nonfounders.\n");
+    return;
+  }
+  uint32_t affected = 0;
+  for (size_t sx = 0; sx < sample_keys.size(); ++sx) {
+    if (S.is_founder[sx] || (included && !(*included)[sx])) {
+      continue;
+    }
+    const uint32_t missing = (present.count(parent_keys[sx].first) ? 0u : 1u) + (present.count(parent_keys[sx].second) ? 0u : 1u);
+    if (missing > (A.make_founders_require2 ? 1u : 0u)) {
+      S.is_founder[sx] = 1;
+      ++affected;
+    }
+  }
+  logprintf("--make-founders: %u sample%s affected.\n", affected, (affected == 1) ? "" : "s");
+}
+
+// --keep, then --remove (KeepOrRemove, plink2_filter.cc:1227-1261; plink2.cc)
+static void keep_remove_samples(Session& S) {
+  const Args& A = S.A;
+  std::vector<uint8_t> in(S.is_founder.size(), 1);
+  for (int pass = 0; pass < 2; ++pass) {
+    const std::vector<std::string>& files = pass ? A.remove_files : A.keep_files;
+    if (files.empty()) {
+      continue;
+    }
+    const char* flag = pass ? "remove" : "keep";
+    std::vector<std::string> keys;
+    for (const std::string& fn : files) {
+      load_sample_id_list(fn, flag, &keys);
+    }
+    std::unordered_set<std::string> listed;
+    size_t dups = 0;
+    for (std::string& k : keys) {
+      dups += listed.insert(std::move(k)).second ? 0 : 1;
+    }
+    uint32_t remaining = 0;
+    for (size_t sx = 0; sx < in.size(); ++sx) {
+      const bool hit = listed.count(S.sample_keys[sx]) != 0;
+      in[sx] = static_cast<uint8_t>(in[sx] && (pass ? !hit : hit));
+      remaining += in[sx];
+    }
+    logprintf("--%s: %u sample%s remaining.\n", flag, remaining, (remaining == 1) ? "" : "s");
+    if (dups) {
+      logprintf("Warning: At least %zu duplicate ID%s in --%s file(s).\n", dups, (dups == 1) ? "" : "s", flag);
+    }
+  }
+  for (size_t sx = 0; sx < in.size(); ++sx) {
+    S.is_founder[sx] = static_cast<uint8_t>(S.is_founder[sx] && in[sx]);
+  }
+  S.sample_kept = in;
+  if (std::find(in.begin(), in.end(), 1) == in.end()) {  // plink2.cc:1836-1838
+    die(13, "Error: No samples remaining after main filters.\n");
+  }
+}
+
+// The samples' stage of load_inputs(): the sample file, --make-founders first, --keep / --remove.  parent_keys: what a later --make-founders needs
+static void load_sample_tables(Session& S, std::vector<std::pair<std::string, std::string>>* parent_keys) {
+  const Args& A = S.A;
+  const bool sample_filter = (!A.keep_files.empty()) || (!A.remove_files.empty());
+  const bool want_keys = sample_filter || A.make_founders || (A.mind < 1.0) || A.rep_smiss() || A.het || A.king;
+  load_samples(A, &S.is_founder, &S.sex, want_keys ? &S.sample_keys : nullptr, A.make_founders ? parent_keys : nullptr, &S.fid_present, &S.sample_sids);
+  if (A.make_founders && A.make_founders_first) {
+    make_founders(S, *parent_keys, nullptr);
+  }
+  if (sample_filter) {
+    keep_remove_samples(S);
+  }
+}
+
+// the genotype file (.bed / fixed-width .pgen / standard variable-width .pgen): --mind needs it earlier than the other stages
+static void open_genotypes(Session& S) {
+  if (S.pg) {
+    return;
+  }
+  const Args& A = S.A;
+  S.is_bed = !A.bed.empty();
+  S.gpath = S.is_bed ? A.bed : A.pgen;
+  if (ldp_pgen_open_indexed(S.gpath.c_str(), A.pgi.empty() ? nullptr : A.pgi.c_str(), static_cast<uint32_t>(S.is_founder.size()), static_cast<uint32_t>(S.V.id.size()), &S.pg)) {
+    die(6, "Error: %s: %s\n", S.gpath.c_str(), ldp_pgen_last_error(S.pg));
+  }
+}
+
+// The early checks of load_inputs(): the tables' log lines, the founder counts the commands need, the genotype file and what its dosages refuse
+static void early_checks(Session& S) {
+  const Args& A = S.A;
+  S.raw_sample_ct = static_cast<uint32_t>(S.is_founder.size());
+  const uint32_t raw_sample_ct = S.raw_sample_ct;
+  const SampleMasks M = sample_masks(S);
+  S.founder_ct += M.founders;
+  const uint32_t founder_ct = S.founder_ct;
+  logprintf("%u sample%s loaded from %s (%u founder%s).\n", raw_sample_ct, raw_sample_ct == 1 ? "" : "s",
+            (A.psam.empty() ? A.fam : A.psam).c_str(), founder_ct, founder_ct == 1 ? "" : "s");
+  S.raw_variant_ct = static_cast<uint32_t>(S.V.id.size());
+  logprintf("%u variant%s loaded from %s.\n", S.raw_variant_ct, S.raw_variant_ct == 1 ? "" : "s", (A.pvar.empty() ? A.bim : A.pvar).c_str());
+
+  if (A.have_prune && founder_ct < 50 && !A.bad_ld) {  // plink2.cc:2063-2071
+    if (raw_sample_ct < 50) {
+      die(13, "Error: This run estimates linkage disequilibrium between variants, but there\nare less than 50 samples to estimate from.  You should perform this operation\non a larger dataset.\n(Strictly speaking, you can also override this error with --bad-ld, but this is\nalmost always a bad idea.)\n");
+    }
+    die(13, "Error: This run estimates linkage disequilibrium between variants, but there\nare less than 50 founders to estimate from.  --make-founders may help.\n(Strictly speaking, you can also override this error with --bad-ld, but this is\nalmost always a bad idea.)\n");
+  }
+  if (A.het && (!A.het_small_sample) && !A.bad_freqs) {  // plink2.cc:2073-2088: --het needs decent allele frequencies (no --read-freq, no --nonfounders here)
+    const uint32_t sample_ct = M.kept_samples;
+    if ((sample_ct >= 50) && (founder_ct < 50)) {
+      die(13, "Error: This run requires decent allele frequencies, but they aren't being\nloaded with --read-freq, and less than 50 founders are available to impute them\nfrom.  Possible solutions:\n* You can use --nonfounders to include nonfounders when imputing allele\n  frequencies.\n* You can generate (with --freq) or obtain an allele frequency file based on a\n  larger similar-population reference dataset, and load it with --read-freq.\n* (Not recommended) You can override this error with --bad-freqs.\n");
+    }
+    if (sample_ct < 50) {
+      die(13, "Error: This run requires decent allele frequencies, but they aren't being\nloaded with --read-freq, and less than 50 samples are available to impute them\nfrom.\nYou should generate (with --freq) or obtain an allele frequency file based on a\nlarger similar-population reference dataset, and load it with --read-freq.\n%s",
+          (sample_ct != founder_ct) ? "If you're certain you want to proceed without doing that, use --bad-freqs to\noverride this error, and consider using --nonfounders as well.\n" : "");
+    }
+  }
+  if ((founder_ct < 2) && (A.have_prune || A.have_r2)) {
+    die(7, "Error: %s requires at least two founders. (--make-founders may come in handy here.)\n", A.have_prune ? (A.pairphase ? "--indep-pairphase" : "--indep-pairwise") : "--r2-unphased");
+  }
+
+  open_genotypes(S);
+  ldp_pgen_info(S.pg, nullptr, nullptr, &S.storage_mode, &S.encoding, &S.has_multiallelic);
+  S.has_dosage = ldp_pgen_has_dosage(S.pg) != 0;
+  if (S.has_dosage) {
+    // The reference takes allele frequencies from the dosages when a file has them (plink2_data.cc:2421-2443).  For
+    // --indep-pairwise that is the major allele's frequency in the tie-break -- r^2 itself is computed from the hardcalls
+    // (plink2_ld.cc:699-723) --, which run_prune() reproduces (ldp_pgen_dosage_sums); --maf / --max-maf compare the same
+    // frequencies.  Everything else that would read dosages (the r^2 of --r2-unphased / --clump, phased dosages) is refused
+    // rather than computed from hardcalls.
+    const char* what = A.have_r2 ? "--r2-unphased / --clump" : (A.pairphase ? "--indep-pairphase" : nullptr);
+    if (what) {
+      ldp_pgen_close(S.pg);
+      die(63, "Error: %s holds dosage data, which plink2-hip reads for --indep-pairwise only (%s would be\ncomputed from hardcalls, unlike plink2).  Use plink2 --make-pgen erase-dosage first.\n", S.gpath.c_str(), what);
+    }
+  }
+  S.rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
+  S.direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(S.pg, &S.rec_bytes));  // NULL for variable-width
+}
+
+// The count filters' stage of load_inputs().  --geno / --maf / --max-maf / --mac / --hwe (and --hardy's report) need genotype counts before the
+// variant list is final: where the job allows it the variants are loaded first and the filters decided from the engine's records (S.device_filter;
+// run_prune: ldp_get_variant_recs + ldp_restrict_variants); otherwise one multi-threaded pass over the rows of the variants the table filters
+// leave (host popcounts; the rows are read again when they go to the device).  Returns, for the host's pass, 1 per raw variant it drops.
+static std::vector<uint8_t> count_filter_stage(Session& S, VariantFilter& filter) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  const bool freq_filter = (A.min_maf != 0.0) || (A.max_maf != 1.0) || (A.min_allele_ddosage != 0) || (A.max_allele_ddosage != ~0ull);
+  const bool hwe_any = A.hwe || A.hardy;
+  std::vector<uint8_t> drop_by_counts;
+  if (!((freq_filter || (A.geno != 1.0) || hwe_any) && (A.have_prune || A.have_r2 || A.het || A.hardy || A.king))) {
+    return drop_by_counts;
+  }
+  std::vector<uint32_t> todo;
+  std::vector<uint8_t> todo_haploid;  // chrY / MT (--hwe / --hardy alone: neither tested nor listed)
+  uint32_t haploid_ct = 0;
+  filter.walk(
+      [&](const std::string& cur, const ChromFacts& c) {
+        if ((!c.out) && (c.cls >= 3) && (freq_filter || (A.geno != 1.0))) {
+          die(63, "Error: --maf / --max-maf / --mac / --max-mac / --geno on chrX, chrY or MT ('%s') are not supported by plink2-hip: filter them out (--autosome, --chr) or pre-filter with plink2.\n", cur.c_str());
+        }
+      },
+      [&](uint32_t v, const ChromFacts& c) {
+        if (c.cls == 3) {  // (.hardy.x and the joint test of females' genotypes and males' alleles are not built)
+          die(63, "Error: --hwe / --hardy with a chrX variant ('%s') are not supported by plink2-hip: filter chrX out (--autosome, --not-chr) or use plink2.\n", V.id[v].c_str());
+        }
+        if (V.alt_ct[v] > 1) {
+          if (hwe_any) {  // (one test per allele against the rest, on genotype counts nobody makes here)
+            die(63, "Error: --hwe / --hardy with a multiallelic variant ('%s') are not supported by plink2-hip: --max-alleles 2 leaves them out.\n", V.id[v].c_str());
+          }
+          die(63, "Error: --maf / --max-maf / --mac / --max-mac / --geno with multiallelic variants ('%s') are not supported by plink2-hip.\n", V.id[v].c_str());
+        }
+        todo.push_back(v);
+        todo_haploid.push_back((c.cls > 3) ? 1 : 0);
+        haploid_ct += (c.cls > 3) ? 1u : 0u;
+      });
+  const SampleMasks M = sample_masks(S);
+  // (--dry-run plans on the final variant list without a device: it takes the host's pass and says which one a run would take.)
+  S.count_filters = true;
+  S.kept_sample_ct = M.kept_samples;
+  S.host_filter_reason = device_filter_refusal(A, S.has_dosage, M.kept_samples, S.founder_ct);
+  if ((!S.host_filter_reason) && haploid_ct) {
+    S.host_filter_reason = "chrY / MT variants among the kept ones (--hwe / --hardy leave them alone; the device's pass takes autosomes only)";
+  }
+  if (A.dry_run) {
+    logprintf("dry-run: variant filters: %s%s\n", S.host_filter_reason ? "host pass: " : "from the device's count pass", S.host_filter_reason ? S.host_filter_reason : "");
+  }
+  S.device_filter = (!S.host_filter_reason) && !A.dry_run;
+  if (S.device_filter) {
+    return drop_by_counts;
+  }
+  const double t_filter0 = now_s();
+  std::vector<RowCounts> counts(todo.size());
+  const bool bed = (S.storage_mode == 0x01);
+  const uint32_t nthreads = host_pass_threads();
+  for_each_row_run(S.pg, S.gpath, S.direct_rows, S.rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
+    count_rows(rows, S.rec_bytes, n, bed, S.raw_sample_ct, M.m_f, M.m_s, &counts[q]);
+  });
+  if (S.has_dosage && freq_filter) {
+    std::vector<uint32_t> with_track;
+    for (uint32_t v : todo) {
+      if (ldp_pgen_variant_has_dosage(S.pg, v)) {
+        with_track.push_back(v);
+      }
+    }
+    S.need_dosage_sums(with_track);
+  }
+  drop_by_counts.assign(S.raw_variant_ct, 0);
+  CountFilters F(A, M.kept_samples);
+  // --hwe / --hardy: ln p of every diploid variant --geno leaves, from the founders' counts, on the reader's threads (ldp_hwe_ln_p_host:
+  // hwe_kernel's arithmetic on the CPU); one set of values serves both where their `midp` settings agree
+  std::vector<double> ln_hwe, ln_hardy;
+  if (hwe_any) {
+    const double t_hwe0 = now_s();
+    const bool two = A.hwe && A.hardy && (A.hwe_midp != A.hardy_midp);
+    const int midp_first = A.hwe ? (A.hwe_midp ? 1 : 0) : (A.hardy_midp ? 1 : 0);
+    ln_hwe.assign(todo.size(), 0.0);
+    if (two) {
+      ln_hardy.assign(todo.size(), 0.0);
+    }
+    std::vector<uint8_t> tie(todo.size(), 0);
+    std::atomic<size_t> next(0);
+    std::vector<std::thread> pool;
+    for (uint32_t t = 0; t < nthreads; ++t) {
+      pool.emplace_back([&]() {
+        for (size_t q0 = next.fetch_add(64); q0 < todo.size(); q0 = next.fetch_add(64)) {
+          for (size_t q = q0; q < std::min(todo.size(), q0 + 64); ++q) {
+            const RowCounts& c = counts[q];
+            if (todo_haploid[q] || F.fails_geno(c.missing)) {
+              continue;
+            }
+            uint8_t fl = 0, fl2 = 0;
+            ln_hwe[q] = ldp_hwe_ln_p_host(static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), midp_first, &fl);
+            if (two) {
+              ln_hardy[q] = ldp_hwe_ln_p_host(static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), A.hardy_midp ? 1 : 0, &fl2);
+            }
+            tie[q] = static_cast<uint8_t>(1 | (((fl | fl2) & 1) << 1));
+          }
+        }
+      });
+    }
+    for (std::thread& th : pool) {
+      th.join();
+    }
+    for (uint8_t x : tie) {
+      S.hwe_host_ct += x & 1;
+      S.hwe_host_ties += x >> 1;
+    }
+    S.hwe_host_s = now_s() - t_hwe0;
+    if (A.timing) {  // (here, not with the pass's own timing: --hwe's strictness error ends the run before that)
+      logprintf("[timing] --hwe / --hardy: host pass (%u p-values from ldp_hwe_ln_p_host on %u threads, %.3f s; %u with a tolerance tie)\n", S.hwe_host_ct, nthreads, S.hwe_host_s,
+                S.hwe_host_ties);
+    }
+  }
+  HardyCounts H;
+  H.haploid_skipped = haploid_ct;
+  for (size_t q = 0; q < todo.size(); ++q) {
+    const RowCounts& c = counts[q];
+    if (A.hardy && (!todo_haploid[q]) && !F.fails_geno(c.missing)) {
+      H.add(todo[q], static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), ln_hardy.empty() ? ln_hwe[q] : ln_hardy[q]);
+    }
+    // (a record with dosages: the founders' dosage sums instead of the hardcalls' allele counts)
+    const auto dd = S.dosage_sums.find(todo[q]);
+    if (F.drops(c.missing, c.ref2, c.het, c.alt2, (dd != S.dosage_sums.end()) ? &dd->second : nullptr, (hwe_any && !todo_haploid[q]) ? &ln_hwe[q] : nullptr)) {
+      drop_by_counts[todo[q]] = 1;
+    }
+  }
+  F.log_counts([&]() {
+    if (A.hardy) {
+      write_hardy(S, H);
+    }
+  });
+  S.host_filter_s = now_s() - t_filter0;
+  if (A.timing) {
+    logprintf("[timing] variant filters: host pass (%.3f s; %s)\n", S.host_filter_s, S.host_filter_reason ? S.host_filter_reason : "--dry-run");
+  }
+  return drop_by_counts;
+}
+
+// The final variant list of load_inputs(): what the table filters and the host's count filters (drop_by_counts; empty: none) leave, with the
+// chromosome order index, chromosome 0 stripped where the reference strips it, and the checks on the whole list (split chromosomes, filters
+// that leave nothing, sortedness)
+static void final_variant_list(Session& S, VariantFilter& filter, const std::vector<uint8_t>& drop_by_counts) {
+  const Args& A = S.A;
+  const Variants& V = S.V;
+  const uint32_t raw_variant_ct = S.raw_variant_ct;
+  const char* table_path = (A.pvar.empty() ? A.bim : A.pvar).c_str();
+  std::vector<uint32_t>&inc = S.inc, &chr_idx = S.chr_idx, &bps = S.bps;
+  uint32_t skipped = 0, after_extract = 0, after_exclude = 0;
+  std::unordered_set<std::string> seen_chr;
+  const ChromFacts* cur = nullptr;
+  uint32_t fo = 0;
+  inc.reserve(raw_variant_ct);
+  chr_idx.reserve(raw_variant_ct);
+  bps.reserve(raw_variant_ct);
+  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
+    if ((!cur) || (V.chrom[v] != V.chrom[v - 1])) {
+      if (!seen_chr.insert(V.chrom[v]).second) {
+        die(6, "Error: %s has a split chromosome. Use --make-pgen + --sort-vars to remedy this.\n", table_path);
+      }
+      fo += cur ? 1 : 0;
+      cur = &filter.chrom(V.chrom[v]);
+    }
+    const VariantFilter::Verdict verdict = filter.verdict(v);
+    if (verdict == VariantFilter::kByTable) {
+      continue;
+    }
+    after_extract += (verdict != VariantFilter::kByExtract) ? 1 : 0;
+    after_exclude += (verdict == VariantFilter::kPass) ? 1 : 0;
+    if ((verdict != VariantFilter::kPass) || ((!drop_by_counts.empty()) && drop_by_counts[v])) {
+      continue;
+    }
+    if (cur->zero && (A.have_prune || (A.r2_table && !A.r2_inter))) {  // (the all-pairs modes keep chromosome 0)
+      if (!S.device_filter) {
+        ++skipped;
+        continue;
+      }
+      // (the count filters see chromosome 0 too, and only what they leave of it is "ignored": such variants are loaded and filtered with
+      // the others, and run_prune() drops and reports the survivors)
+      S.inc_chr0.resize(inc.size() + 1, 0);
+      S.inc_chr0.back() = 1;
+    }
+    if (cur->cls == 2) {
+      die(6, "Error: Invalid chromosome code '%s'. (Use --allow-extra-chr to force it to be accepted.)\n", V.chrom[v].c_str());
+    }
+    S.vcls.push_back(static_cast<uint8_t>(cur->cls));
+    inc.push_back(v);
+    chr_idx.push_back(fo);
+    bps.push_back(V.bp[v]);
+  }
+  if (!A.extract_files.empty()) {
+    logprintf("--extract: %u variant%s remaining.\n", after_extract, (after_extract == 1) ? "" : "s");
+  }
+  if (!A.exclude_files.empty()) {
+    logprintf("--exclude: %u variant%s remaining.\n", after_exclude, (after_exclude == 1) ? "" : "s");
+  }
+  // filters applied while the variant table loads (--autosome / --chr / --not-chr / --max-alleles) that leave nothing:
+  // plink2.cc:1025-1050, kPglRetInconsistentInput, flag names in kLoadFilterLogFlagnames order
+  const bool table_filter = filter.by_chrom || (A.max_alleles != 0xffffffffu) || A.snps_only;
+  if (table_filter && raw_variant_ct) {
+    bool any_loaded = false;
+    for (uint32_t v = 0; (v < raw_variant_ct) && !any_loaded; ++v) {
+      any_loaded = filter.table_passes(v);
+    }
+    if (!any_loaded) {
+      std::string flags;
+      for (const char* nm : {A.autosome ? "autosome" : "", A.chr_keep.empty() ? "" : "chr", A.chr_drop.empty() ? "" : "not-chr",
+                             (A.max_alleles != 0xffffffffu) ? "max-alleles" : "", A.snps_only ? "snps-only" : ""}) {
+        if (*nm) {
+          flags += (flags.empty() ? "--" : " + --");
+          flags += nm;
+        }
+      }
+      die(7, "Error: All %u variant%s in %s excluded by %s.\n", raw_variant_ct, (raw_variant_ct == 1) ? "" : "s", table_path, flags.c_str());
+    }
+  }
+  const bool any_main_filter = table_filter || (!A.extract_files.empty()) || (!A.exclude_files.empty()) || (!drop_by_counts.empty()) || S.device_filter;
+  if (any_main_filter && inc.empty() && (!skipped)) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
+    die(13, "Error: No variants remaining after main filters.\n");
+  }
+  if (skipped) {
+    logprintf("--%s: Ignoring %u chromosome 0 variant%s.\n", A.have_prune ? (A.pairphase ? "indep-pairphase" : "indep-pairwise") : (A.have_clump ? "clump" : "r2-unphased"), skipped, skipped == 1 ? "" : "s");
+  }
+  S.variant_ct = static_cast<uint32_t>(inc.size());
+  if ((A.window_is_bp || A.r2_table) && !S.device_filter) {  // (device_filter: the check is about the variants the count filters leave, run_prune())
+    for (uint32_t k = 1; k < S.variant_ct; ++k) {
+      if (chr_idx[k] == chr_idx[k - 1] && bps[k] < bps[k - 1]) {
+        if (A.have_prune) {  // plink2.cc:2926-2929
+          die(6, "Error: When the window size is in kb units, LD-based pruning requires a sorted\n.pvar/.bim.  Retry this command after using --make-pgen/--make-bed +\n--sort-vars to sort your data.\n");
+        }
+        if (A.have_clump) {  // plink2.cc:2998-3001
+          die(7, "Error: --clump requires a sorted .pvar/.bim.  Retry this command after using\n--make-pgen/--make-bed + --sort-vars to sort your data.\n");
+        }
+        die(6, "Error: --r[2]-[un]phased runs require a sorted .pvar/.bim.  Retry this command\nafter using --make-pgen/--make-bed + --sort-vars to sort your data.\n");  // plink2.cc:2944-2947
+      }
+    }
+  }
+}
+
+// chrX and chrY variants run on engines of their own (different sample sets); MT stays with the autosomes --
+// except under --indep-pairphase, where the autosomes carry two haplotypes per founder and MT one
+// (IndepPairphaseUpdateSubcontig, plink2_ld.cc:1491-1511)
+static void split_into_engines(Session& S) {
+  for (uint32_t k = 0; k < S.variant_ct; ++k) {
+    (S.vcls[k] == 3 ? S.xk : (S.vcls[k] == 4 ? S.yk : ((S.vcls[k] == 5 && S.A.pairphase) ? S.tk : S.mk))).push_back(k);
+  }
+  S.m_ct = static_cast<uint32_t>(S.mk.size());
+  S.m_chr.resize(S.m_ct);
+  S.m_bps.resize(S.m_ct);
+  for (uint32_t q = 0; q < S.m_ct; ++q) {
+    S.m_chr[q] = S.chr_idx[S.mk[q]];
+    S.m_bps[q] = S.bps[S.mk[q]];
+  }
+}
+
 void load_inputs(Session& S, int argc, char** argv) {
   S.t_begin = S.t_begin_first ? S.t_begin_first : now_s();
   S.A = parse_args(argc, argv);
   const Args& A = S.A;
-  const double t_begin = S.t_begin;
   if (!g_log) {
     g_log = fopen((A.out + ".log").c_str(), "w");
   }
@@ -943,528 +1326,61 @@ void load_inputs(Session& S, int argc, char** argv) {
 
   // the variant table parses on its own thread and the HIP runtime initialises on another while the
   // sample file is read
-  Variants& V = S.V;
-  std::thread t_variants([&]() { load_variants(A, &V); });
+  std::thread t_variants([&S]() { load_variants(S.A, &S.V); });
   // (the HIP runtime start-up AND the context of device 0 -- its queues, the first pinned allocation -- beside the table parsing)
   S.t_joined = now_s();   // (a restarted run: the runtime is up, there is nothing to start or to join)
   if (!S.mind_decided) {
     S.t_hip = std::thread([&S]() { const double t0 = now_s(); if (ldp_device_count() > 0) { (void)ldp_prewarm(0); } S.t_hip_init = now_s() - t0; });
   }
-  std::vector<uint8_t>& is_founder = S.is_founder;
-  std::vector<std::string>& sample_keys = S.sample_keys;
-  const bool sample_filter = (!A.keep_files.empty()) || (!A.remove_files.empty());
-  const bool mind_on = (A.mind < 1.0);  // plink2.cc:8910
   std::vector<std::pair<std::string, std::string>> parent_keys;
-  load_samples(A, &S.is_founder, &S.sex, (sample_filter || A.make_founders || mind_on || A.rep_smiss() || A.het || A.king) ? &sample_keys : nullptr, A.make_founders ? &parent_keys : nullptr, &S.fid_present,
-               &S.sample_sids);
-  // --make-founders (MakeFounders, plink2_filter.cc:4372-4443): a non-founder with a parent (both, with 'require-2-missing') that
-  // is not among the samples in play becomes a founder; 'first' applies it before --keep / --remove, else after them
-  auto make_founders = [&](const std::vector<uint8_t>* included) {
-    std::unordered_set<std::string> present;
-    bool any_nonfounder = false;
-    for (size_t sx = 0; sx < sample_keys.size(); ++sx) {
-      if ((!included) || (*included)[sx]) {
-        present.insert(sample_keys[sx]);
-        any_nonfounder = any_nonfounder || !S.is_founder[sx];
-      }
-    }
-    if (!any_nonfounder) {
-      logprintf("Note: Skipping --make-founders since there are no nonfounders.\n");
-      return;
-    }
-    uint32_t affected = 0;
-    for (size_t sx = 0; sx < sample_keys.size(); ++sx) {
-      if (S.is_founder[sx] || (included && !(*included)[sx])) {
-        continue;
-      }
-      const uint32_t missing = (present.count(parent_keys[sx].first) ? 0u : 1u) + (present.count(parent_keys[sx].second) ? 0u : 1u);
-      if (missing > (A.make_founders_require2 ? 1u : 0u)) {
-        S.is_founder[sx] = 1;
-        ++affected;
-      }
-    }
-    logprintf("--make-founders: %u sample%s affected.\n", affected, (affected == 1) ? "" : "s");
-  };
-  if (A.make_founders && A.make_founders_first) {
-    make_founders(nullptr);
-  }
-  if (sample_filter) {  // KeepOrRemove, plink2_filter.cc:1227-1261 (--keep first, then --remove, plink2.cc)
-    std::vector<uint8_t> in(S.is_founder.size(), 1);
-    for (int pass = 0; pass < 2; ++pass) {
-      const std::vector<std::string>& files = pass ? A.remove_files : A.keep_files;
-      if (files.empty()) {
-        continue;
-      }
-      const char* flag = pass ? "remove" : "keep";
-      std::vector<std::string> keys;
-      for (const std::string& fn : files) {
-        load_sample_id_list(fn, flag, &keys);
-      }
-      std::unordered_set<std::string> listed;
-      size_t dups = 0;
-      for (std::string& k : keys) {
-        dups += listed.insert(std::move(k)).second ? 0 : 1;
-      }
-      uint32_t remaining = 0;
-      for (size_t sx = 0; sx < in.size(); ++sx) {
-        const bool hit = listed.count(sample_keys[sx]) != 0;
-        in[sx] = static_cast<uint8_t>(in[sx] && (pass ? !hit : hit));
-        remaining += in[sx];
-      }
-      logprintf("--%s: %u sample%s remaining.\n", flag, remaining, (remaining == 1) ? "" : "s");
-      if (dups) {
-        logprintf("Warning: At least %zu duplicate ID%s in --%s file(s).\n", dups, (dups == 1) ? "" : "s", flag);
-      }
-    }
-    for (size_t sx = 0; sx < in.size(); ++sx) {
-      S.is_founder[sx] = static_cast<uint8_t>(S.is_founder[sx] && in[sx]);
-    }
-    S.sample_kept = in;
-    if (std::find(in.begin(), in.end(), 1) == in.end()) {  // plink2.cc:1836-1838
-      die(13, "Error: No samples remaining after main filters.\n");
-    }
-  }
-  // ---- what --mind needs earlier than the other filters, and they where they always were: the genotype file (.bed / fixed-width .pgen / standard
-  // variable-width .pgen) and the --extract / --exclude ID sets
-  ldp_pgen*& pg = S.pg;
-  auto open_genotypes = [&]() {
-    if (pg) {
-      return;
-    }
-    S.is_bed = !A.bed.empty();
-    S.gpath = S.is_bed ? A.bed : A.pgen;
-    if (ldp_pgen_open_indexed(S.gpath.c_str(), A.pgi.empty() ? nullptr : A.pgi.c_str(), static_cast<uint32_t>(is_founder.size()), static_cast<uint32_t>(V.id.size()), &pg)) {
-      die(6, "Error: %s: %s\n", S.gpath.c_str(), ldp_pgen_last_error(pg));
-    }
-  };
-  std::unordered_set<std::string> extract_ids, exclude_ids;
-  bool id_sets_loaded = false;
-  auto load_id_sets = [&]() {
-    if (id_sets_loaded) {
-      return;
-    }
-    id_sets_loaded = true;
-    for (const std::string& fn : A.extract_files) {
-      for (std::string& t : tokens_of_file(fn)) {
-        extract_ids.insert(std::move(t));
-      }
-    }
-    for (const std::string& fn : A.exclude_files) {
-      for (std::string& t : tokens_of_file(fn)) {
-        exclude_ids.insert(std::move(t));
-      }
-    }
-  };
-  const bool chr_filter = (!A.chr_keep.empty()) || (!A.chr_drop.empty()) || A.autosome;
-  // ---- --mind: after --keep / --remove, before --make-founders (unless 'first'), --geno and the founder count (plink2.cc:1600-1840)
-  if (mind_on) {
+  load_sample_tables(S, &parent_keys);
+  // ---- --mind: after --keep / --remove, before --make-founders (unless 'first'), --geno and the founder count (plink2.cc:1600-1840).  It needs
+  // the genotype file and the variant-table filter -- the --extract / --exclude ID sets -- earlier than the other stages, and they where they always were
+  std::optional<VariantFilter> filter;
+  if (A.mind < 1.0) {  // plink2.cc:8910
     t_variants.join();
-    open_genotypes();
-    load_id_sets();
-    sample_filter_mind(S, chr_filter, extract_ids, exclude_ids);
+    open_genotypes(S);
+    filter.emplace(A, S.V);
+    sample_filter_mind(S, *filter);
   }
   if (A.make_founders && !A.make_founders_first) {
-    make_founders(S.sample_kept.empty() ? nullptr : &S.sample_kept);
+    make_founders(S, parent_keys, S.sample_kept.empty() ? nullptr : &S.sample_kept);
   }
   if (t_variants.joinable()) {
     t_variants.join();
   }
-  S.t_parse = now_s() - t_begin;
-  S.raw_sample_ct = static_cast<uint32_t>(is_founder.size());
-  const uint32_t raw_sample_ct = S.raw_sample_ct;
-  uint32_t& founder_ct = S.founder_ct;
-  for (uint8_t f : is_founder) {
-    founder_ct += f;
-  }
-  logprintf("%u sample%s loaded from %s (%u founder%s).\n", raw_sample_ct, raw_sample_ct == 1 ? "" : "s",
-            (A.psam.empty() ? A.fam : A.psam).c_str(), founder_ct, founder_ct == 1 ? "" : "s");
-  S.raw_variant_ct = static_cast<uint32_t>(V.id.size());
-  const uint32_t raw_variant_ct = S.raw_variant_ct;
-  logprintf("%u variant%s loaded from %s.\n", raw_variant_ct, raw_variant_ct == 1 ? "" : "s", (A.pvar.empty() ? A.bim : A.pvar).c_str());
+  S.t_parse = now_s() - S.t_begin;
+  early_checks(S);
 
-  if (A.have_prune && founder_ct < 50 && !A.bad_ld) {  // plink2.cc:2063-2071
-    if (raw_sample_ct < 50) {
-      die(13, "Error: This run estimates linkage disequilibrium between variants, but there\nare less than 50 samples to estimate from.  You should perform this operation\non a larger dataset.\n(Strictly speaking, you can also override this error with --bad-ld, but this is\nalmost always a bad idea.)\n");
-    }
-    die(13, "Error: This run estimates linkage disequilibrium between variants, but there\nare less than 50 founders to estimate from.  --make-founders may help.\n(Strictly speaking, you can also override this error with --bad-ld, but this is\nalmost always a bad idea.)\n");
+  // ---- variant filters: --chr / --not-chr / --autosome by chromosome, --max-alleles, --snps-only, then --extract, then --exclude by ID
+  if (!filter) {
+    filter.emplace(A, S.V);
   }
-  if (A.het && (!A.het_small_sample) && !A.bad_freqs) {  // plink2.cc:2073-2088: --het needs decent allele frequencies (no --read-freq, no --nonfounders here)
-    uint32_t sample_ct = 0;
-    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-      sample_ct += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
-    }
-    if ((sample_ct >= 50) && (founder_ct < 50)) {
-      die(13, "Error: This run requires decent allele frequencies, but they aren't being\nloaded with --read-freq, and less than 50 founders are available to impute them\nfrom.  Possible solutions:\n* You can use --nonfounders to include nonfounders when imputing allele\n  frequencies.\n* You can generate (with --freq) or obtain an allele frequency file based on a\n  larger similar-population reference dataset, and load it with --read-freq.\n* (Not recommended) You can override this error with --bad-freqs.\n");
-    }
-    if (sample_ct < 50) {
-      die(13, "Error: This run requires decent allele frequencies, but they aren't being\nloaded with --read-freq, and less than 50 samples are available to impute them\nfrom.\nYou should generate (with --freq) or obtain an allele frequency file based on a\nlarger similar-population reference dataset, and load it with --read-freq.\n%s",
-          (sample_ct != founder_ct) ? "If you're certain you want to proceed without doing that, use --bad-freqs to\noverride this error, and consider using --nonfounders as well.\n" : "");
-    }
-  }
-  if ((founder_ct < 2) && (A.have_prune || A.have_r2)) {
-    die(7, "Error: %s requires at least two founders. (--make-founders may come in handy here.)\n", A.have_prune ? (A.pairphase ? "--indep-pairphase" : "--indep-pairwise") : "--r2-unphased");
-  }
-
-  open_genotypes();
-  const std::string& gpath = S.gpath;
-  ldp_pgen_info(pg, nullptr, nullptr, &S.storage_mode, &S.encoding, &S.has_multiallelic);
-  S.has_dosage = ldp_pgen_has_dosage(pg) != 0;
-  if (S.has_dosage) {
-    // The reference takes allele frequencies from the dosages when a file has them (plink2_data.cc:2421-2443).  For
-    // --indep-pairwise that is the major allele's frequency in the tie-break -- r^2 itself is computed from the hardcalls
-    // (plink2_ld.cc:699-723) --, which run_prune() reproduces (ldp_pgen_dosage_sums); --maf / --max-maf compare the same
-    // frequencies.  Everything else that would read dosages (the r^2 of --r2-unphased / --clump, phased dosages) is refused
-    // rather than computed from hardcalls.
-    const char* what = A.have_r2 ? "--r2-unphased / --clump" : (A.pairphase ? "--indep-pairphase" : nullptr);
-    if (what) {
-      ldp_pgen_close(pg);
-      die(63, "Error: %s holds dosage data, which plink2-hip reads for --indep-pairwise only (%s would be\ncomputed from hardcalls, unlike plink2).  Use plink2 --make-pgen erase-dosage first.\n", gpath.c_str(), what);
-    }
-  }
-  S.rec_bytes = (static_cast<uint64_t>(raw_sample_ct) + 3) / 4;
-  S.direct_rows = static_cast<const uint8_t*>(ldp_pgen_direct_rows(pg, &S.rec_bytes));  // NULL for variable-width
-
-  // ---- variant table: strip chromosome 0, chromosome order index, sortedness, unique IDs
-  std::vector<uint32_t>& inc = S.inc;
-  std::vector<uint32_t>& chr_idx = S.chr_idx;
-  std::vector<uint32_t>& bps = S.bps;
-  std::vector<uint8_t>& vcls = S.vcls;
-  uint32_t skipped = 0;
-  // variant filters: --chr / --not-chr / --autosome by chromosome, then --extract, then --exclude by ID
-  // (TokenExtractExclude, plink2_filter.cc:367: every variant carrying a listed ID, unknown IDs ignored)
-  load_id_sets();
-  uint32_t after_extract = 0, after_exclude = 0;
-  // --geno / --maf / --max-maf need genotype counts before the variant list is final: one multi-threaded pass over the rows of
-  // the variants the table filters leave (host popcounts; the rows are read again when they go to the device)
-  std::vector<uint8_t> drop_by_counts;
-  const bool mac_filter = (A.min_allele_ddosage != 0) || (A.max_allele_ddosage != ~0ull);
-  const bool freq_filter = (A.min_maf != 0.0) || (A.max_maf != 1.0) || mac_filter;
-  if (mac_filter && (!A.ac_founders)) {
+  if (((A.min_allele_ddosage != 0) || (A.max_allele_ddosage != ~0ull)) && (!A.ac_founders) && (sample_masks(S).kept_samples != S.founder_ct)) {
     // (plink2.cc:2102-2105; plink2-hip counts alleles over the founders: the --nonfounders alternative is not offered)
-    uint32_t kept = 0;
-    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-      kept += (S.sample_kept.empty() || S.sample_kept[sx]) ? 1u : 0u;
-    }
-    if (kept != founder_ct) {
-      die(7, "Error: --mac/--max-mac/\"--freq counts\" specified, but with neither\n--ac-founders nor --nonfounders; and nonfounders are present.\n");
-    }
+    die(7, "Error: --mac/--max-mac/\"--freq counts\" specified, but with neither\n--ac-founders nor --nonfounders; and nonfounders are present.\n");
   }
   // ---- the count reports: after the sample filters, before --geno / --maf / --mac (plink2.cc:2370-2470)
   if (A.any_report()) {
-    reports_stage(S, chr_filter, extract_ids, exclude_ids);
+    reports_stage(S, *filter);
   }
   // (a run of reports alone: nothing reads the filtered variant list, and the reference applies no variant filter then)
   if (A.het) {
-    het_stage(S, chr_filter, extract_ids, exclude_ids);
+    het_stage(S, *filter);
   }
   if (A.king) {
-    king_stage(S, chr_filter, extract_ids, exclude_ids);
+    king_stage(S, *filter);
   }
-  const bool hwe_any = A.hwe || A.hardy;
-  if ((freq_filter || (A.geno != 1.0) || hwe_any) && (A.have_prune || A.have_r2 || A.het || A.hardy || A.king)) {
-    std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome, 2 = chrX, 4 = chrY / MT (--hwe / --hardy alone: neither tested nor listed)
-    std::vector<uint32_t> todo;
-    std::vector<uint8_t> todo_haploid;
-    uint32_t haploid_ct = 0;
-    for (uint32_t v = 0; v < raw_variant_ct; ++v) {
-      auto it = chr_state.find(V.chrom[v]);
-      if (it == chr_state.end()) {
-        const std::string& cur = V.chrom[v];
-        const int code = chrom_code(cur);
-        const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                                         (A.autosome && !((code >= 1) && (code <= 22))));
-        bool zero = false;
-        const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
-        if ((!out) && (cls >= 3) && (freq_filter || (A.geno != 1.0))) {
-          die(63, "Error: --maf / --max-maf / --mac / --max-mac / --geno on chrX, chrY or MT ('%s') are not supported by plink2-hip: filter them out (--autosome, --chr) or pre-filter with plink2.\n", cur.c_str());
-        }
-        it = chr_state.emplace(cur, static_cast<uint8_t>((out ? 1 : 0) | ((cls == 3) ? 2 : 0) | ((cls > 3) ? 4 : 0))).first;
-      }
-      if ((it->second & 1) || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
-        continue;
-      }
-      if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
-        continue;
-      }
-      if (it->second & 2) {  // (.hardy.x and the joint test of females' genotypes and males' alleles are not built)
-        die(63, "Error: --hwe / --hardy with a chrX variant ('%s') are not supported by plink2-hip: filter chrX out (--autosome, --not-chr) or use plink2.\n", V.id[v].c_str());
-      }
-      if (V.alt_ct[v] > 1) {
-        if (hwe_any) {  // (one test per allele against the rest, on genotype counts nobody makes here)
-          die(63, "Error: --hwe / --hardy with a multiallelic variant ('%s') are not supported by plink2-hip: --max-alleles 2 leaves them out.\n", V.id[v].c_str());
-        }
-        die(63, "Error: --maf / --max-maf / --mac / --max-mac / --geno with multiallelic variants ('%s') are not supported by plink2-hip.\n", V.id[v].c_str());
-      }
-      todo.push_back(v);
-      todo_haploid.push_back((it->second & 4) ? 1 : 0);
-      haploid_ct += (it->second & 4) ? 1u : 0u;
-    }
-    const size_t words = (static_cast<size_t>(raw_sample_ct) + 31) / 32;
-    std::vector<uint64_t> m_f(words, 0), m_s(words, 0);
-    uint32_t kept_samples = 0;
-    for (uint32_t sx = 0; sx < raw_sample_ct; ++sx) {
-      if (S.sample_kept.empty() || S.sample_kept[sx]) {
-        m_s[sx >> 5] |= 1ull << (2 * (sx & 31));
-        ++kept_samples;
-      }
-      if (is_founder[sx]) {
-        m_f[sx >> 5] |= 1ull << (2 * (sx & 31));
-      }
-    }
-    // The engine's count pass makes the same counts a moment later, on the device: where the job allows it the variants are loaded
-    // first and the filters decided from its records (run_prune: ldp_get_variant_recs + ldp_restrict_variants), and this pass is skipped.
-    // (--dry-run plans on the final variant list without a device: it takes the pass and says which one a run would take.)
-    S.count_filters = true;
-    S.kept_sample_ct = kept_samples;
-    S.host_filter_reason = device_filter_refusal(A, S.has_dosage, kept_samples, founder_ct);
-    if ((!S.host_filter_reason) && haploid_ct) {
-      S.host_filter_reason = "chrY / MT variants among the kept ones (--hwe / --hardy leave them alone; the device's pass takes autosomes only)";
-    }
-    if (A.dry_run) {
-      logprintf("dry-run: variant filters: %s%s\n", S.host_filter_reason ? "host pass: " : "from the device's count pass", S.host_filter_reason ? S.host_filter_reason : "");
-    }
-    S.device_filter = (!S.host_filter_reason) && !A.dry_run;
-    const double t_filter0 = now_s();
-    if (!S.device_filter) {
-      std::vector<RowCounts> counts(todo.size());
-      const bool bed = (S.storage_mode == 0x01);
-      const uint32_t nthreads = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-      for_each_row_run(pg, gpath, S.direct_rows, S.rec_bytes, todo, nthreads, [&](uint32_t, const uint8_t* rows, uint32_t n, size_t q) {
-        count_rows(rows, S.rec_bytes, n, bed, raw_sample_ct, m_f, m_s, &counts[q]);
-      });
-      if (S.has_dosage && freq_filter) {
-        std::vector<uint32_t> with_track;
-        for (uint32_t v : todo) {
-          if (ldp_pgen_variant_has_dosage(pg, v)) {
-            with_track.push_back(v);
-          }
-        }
-        S.need_dosage_sums(with_track);
-      }
-      drop_by_counts.assign(raw_variant_ct, 0);
-      CountFilters F(A, kept_samples);
-      // --hwe / --hardy: ln p of every diploid variant --geno leaves, from the founders' counts, on the reader's threads (ldp_hwe_ln_p_host:
-      // hwe_kernel's arithmetic on the CPU); one set of values serves both where their `midp` settings agree
-      std::vector<double> ln_hwe, ln_hardy;
-      if (hwe_any) {
-        const double t_hwe0 = now_s();
-        const bool two = A.hwe && A.hardy && (A.hwe_midp != A.hardy_midp);
-        const int midp_first = A.hwe ? (A.hwe_midp ? 1 : 0) : (A.hardy_midp ? 1 : 0);
-        ln_hwe.assign(todo.size(), 0.0);
-        if (two) {
-          ln_hardy.assign(todo.size(), 0.0);
-        }
-        std::vector<uint8_t> tie(todo.size(), 0);
-        std::atomic<size_t> next(0);
-        std::vector<std::thread> pool;
-        for (uint32_t t = 0; t < nthreads; ++t) {
-          pool.emplace_back([&]() {
-            for (size_t q0 = next.fetch_add(64); q0 < todo.size(); q0 = next.fetch_add(64)) {
-              for (size_t q = q0; q < std::min(todo.size(), q0 + 64); ++q) {
-                const RowCounts& c = counts[q];
-                if (todo_haploid[q] || F.fails_geno(c.missing)) {
-                  continue;
-                }
-                uint8_t fl = 0, fl2 = 0;
-                ln_hwe[q] = ldp_hwe_ln_p_host(static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), midp_first, &fl);
-                if (two) {
-                  ln_hardy[q] = ldp_hwe_ln_p_host(static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), A.hardy_midp ? 1 : 0, &fl2);
-                }
-                tie[q] = static_cast<uint8_t>(1 | (((fl | fl2) & 1) << 1));
-              }
-            }
-          });
-        }
-        for (std::thread& th : pool) {
-          th.join();
-        }
-        for (uint8_t x : tie) {
-          S.hwe_host_ct += x & 1;
-          S.hwe_host_ties += x >> 1;
-        }
-        S.hwe_host_s = now_s() - t_hwe0;
-        if (A.timing) {  // (here, not with the pass's own timing: --hwe's strictness error ends the run before that)
-          logprintf("[timing] --hwe / --hardy: host pass (%u p-values from ldp_hwe_ln_p_host on %u threads, %.3f s; %u with a tolerance tie)\n", S.hwe_host_ct, nthreads, S.hwe_host_s,
-                    S.hwe_host_ties);
-        }
-      }
-      HardyCounts H;
-      H.haploid_skipped = haploid_ct;
-      for (size_t q = 0; q < todo.size(); ++q) {
-        const RowCounts& c = counts[q];
-        if (A.hardy && (!todo_haploid[q]) && !F.fails_geno(c.missing)) {
-          H.add(todo[q], static_cast<uint32_t>(c.ref2), static_cast<uint32_t>(c.het), static_cast<uint32_t>(c.alt2), ln_hardy.empty() ? ln_hwe[q] : ln_hardy[q]);
-        }
-        // (a record with dosages: the founders' dosage sums instead of the hardcalls' allele counts)
-        const auto dd = S.dosage_sums.find(todo[q]);
-        if (F.drops(c.missing, c.ref2, c.het, c.alt2, (dd != S.dosage_sums.end()) ? &dd->second : nullptr, (hwe_any && !todo_haploid[q]) ? &ln_hwe[q] : nullptr)) {
-          drop_by_counts[todo[q]] = 1;
-        }
-      }
-      F.log_counts([&]() {
-        if (A.hardy) {
-          write_hardy(S, H);
-        }
-      });
-      S.host_filter_s = now_s() - t_filter0;
-      if (A.timing) {
-        logprintf("[timing] variant filters: host pass (%.3f s; %s)\n", S.host_filter_s, S.host_filter_reason ? S.host_filter_reason : "--dry-run");
-      }
-    }
-  }
-  if (S.report_device && !S.device_filter) {
-    S.device_filter = true;  // (as for --mind below: every listed row is loaded under the all-pairs plan, run_prune() writes the reports and plans afterwards)
-    S.kept_sample_ct = founder_ct;
-  }
-  if (S.mind_device && !S.device_filter) {
-    // (no count filter, or none that reached the block above: the rows --mind counts over are loaded under the all-pairs plan all the same, chromosome 0
-    // included, and run_prune() plans over what is left once the samples are decided)
+  const std::vector<uint8_t> drop_by_counts = count_filter_stage(S, *filter);
+  if ((S.report_device || S.mind_device || S.het_device || S.king_device) && !S.device_filter) {
+    // (no count filter, or none that reached the device: the rows the reports, --mind, --het or --make-king-table read off the image are loaded under the
+    // all-pairs plan all the same, chromosome 0 included; run_prune() writes what they write and plans over what is left afterwards)
     S.device_filter = true;
-    S.kept_sample_ct = founder_ct;
+    S.kept_sample_ct = S.founder_ct;
   }
-  if (S.het_device && !S.device_filter) {  // (the same again: --het reads the image after the filters, whoever decided them)
-    S.device_filter = true;
-    S.kept_sample_ct = founder_ct;
-  }
-  if (S.king_device && !S.device_filter) {  // (... and --make-king-table)
-    S.device_filter = true;
-    S.kept_sample_ct = founder_ct;
-  }
-  {
-    std::unordered_set<std::string> seen_chr;
-    std::string cur;
-    uint32_t fo = 0;
-    bool first = true;
-    bool zero = false;
-    bool chr_out = false;
-    int cls = 0;
-    inc.reserve(raw_variant_ct);
-    chr_idx.reserve(raw_variant_ct);
-    bps.reserve(raw_variant_ct);
-    for (uint32_t v = 0; v < raw_variant_ct; ++v) {
-      if (first || V.chrom[v] != cur) {
-        if (!seen_chr.insert(V.chrom[v]).second) {
-          die(6, "Error: %s has a split chromosome. Use --make-pgen + --sort-vars to remedy this.\n", (A.pvar.empty() ? A.bim : A.pvar).c_str());
-        }
-        cur = V.chrom[v];
-        if (!first) {
-          ++fo;
-        }
-        first = false;
-        cls = chrom_class(cur, A.allow_extra_chr, &zero);
-        chr_out = false;
-        if (chr_filter) {
-          const int code = chrom_code(cur);
-          chr_out = ((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                    (A.autosome && !((code >= 1) && (code <= 22)));
-        }
-      }
-      if (chr_out || ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v]))) {
-        continue;
-      }
-      if ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) {
-        continue;
-      }
-      ++after_extract;
-      if ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v])) {
-        continue;
-      }
-      ++after_exclude;
-      if ((!drop_by_counts.empty()) && drop_by_counts[v]) {
-        continue;
-      }
-      if (zero && (A.have_prune || (A.r2_table && !A.r2_inter))) {  // (the all-pairs modes keep chromosome 0)
-        if (!S.device_filter) {
-          ++skipped;
-          continue;
-        }
-        // (the count filters see chromosome 0 too, and only what they leave of it is "ignored": such variants are loaded and filtered with
-        // the others, and run_prune() drops and reports the survivors)
-        S.inc_chr0.resize(inc.size() + 1, 0);
-        S.inc_chr0.back() = 1;
-      }
-      if (cls == 2) {
-        die(6, "Error: Invalid chromosome code '%s'. (Use --allow-extra-chr to force it to be accepted.)\n", cur.c_str());
-      }
-      vcls.push_back(static_cast<uint8_t>(cls));
-      inc.push_back(v);
-      chr_idx.push_back(fo);
-      bps.push_back(V.bp[v]);
-    }
-  }
-  if (!A.extract_files.empty()) {
-    logprintf("--extract: %u variant%s remaining.\n", after_extract, (after_extract == 1) ? "" : "s");
-  }
-  if (!A.exclude_files.empty()) {
-    logprintf("--exclude: %u variant%s remaining.\n", after_exclude, (after_exclude == 1) ? "" : "s");
-  }
-  // filters applied while the variant table loads (--autosome / --chr / --not-chr / --max-alleles) that leave nothing:
-  // plink2.cc:1025-1050, kPglRetInconsistentInput, flag names in kLoadFilterLogFlagnames order
-  if ((chr_filter || (A.max_alleles != 0xffffffffu) || A.snps_only) && raw_variant_ct) {
-    bool any_loaded = false;
-    std::unordered_map<std::string, uint8_t> chr_state;
-    for (uint32_t v = 0; (v < raw_variant_ct) && !any_loaded; ++v) {
-      auto it = chr_state.find(V.chrom[v]);
-      if (it == chr_state.end()) {
-        const std::string& cur = V.chrom[v];
-        const int code = chrom_code(cur);
-        const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                                         (A.autosome && !((code >= 1) && (code <= 22))));
-        it = chr_state.emplace(cur, static_cast<uint8_t>(out)).first;
-      }
-      any_loaded = (!it->second) && (allele_ct_for_filter(V, v) <= A.max_alleles) && !(A.snps_only && V.not_snp[v]);
-    }
-    if (!any_loaded) {
-      std::string flags;
-      for (const char* nm : {A.autosome ? "autosome" : "", A.chr_keep.empty() ? "" : "chr", A.chr_drop.empty() ? "" : "not-chr",
-                             (A.max_alleles != 0xffffffffu) ? "max-alleles" : "", A.snps_only ? "snps-only" : ""}) {
-        if (*nm) {
-          flags += (flags.empty() ? "--" : " + --");
-          flags += nm;
-        }
-      }
-      die(7, "Error: All %u variant%s in %s excluded by %s.\n", raw_variant_ct, (raw_variant_ct == 1) ? "" : "s", (A.pvar.empty() ? A.bim : A.pvar).c_str(), flags.c_str());
-    }
-  }
-  const bool any_main_filter = chr_filter || (!A.extract_files.empty()) || (!A.exclude_files.empty()) || (!drop_by_counts.empty()) || S.device_filter || (A.max_alleles != 0xffffffffu) || A.snps_only;
-  if (any_main_filter && inc.empty() && (!skipped)) {  // plink2.cc:2484-2487 (kPglRetDegenerateData)
-    die(13, "Error: No variants remaining after main filters.\n");
-  }
-  if (skipped) {
-    logprintf("--%s: Ignoring %u chromosome 0 variant%s.\n", A.have_prune ? (A.pairphase ? "indep-pairphase" : "indep-pairwise") : (A.have_clump ? "clump" : "r2-unphased"), skipped, skipped == 1 ? "" : "s");
-  }
-  S.variant_ct = static_cast<uint32_t>(inc.size());
-  const uint32_t variant_ct = S.variant_ct;
-  if ((A.window_is_bp || A.r2_table) && !S.device_filter) {  // (device_filter: the check is about the variants the count filters leave, run_prune())
-    for (uint32_t k = 1; k < variant_ct; ++k) {
-      if (chr_idx[k] == chr_idx[k - 1] && bps[k] < bps[k - 1]) {
-        if (A.have_prune) {  // plink2.cc:2926-2929
-          die(6, "Error: When the window size is in kb units, LD-based pruning requires a sorted\n.pvar/.bim.  Retry this command after using --make-pgen/--make-bed +\n--sort-vars to sort your data.\n");
-        }
-        if (A.have_clump) {  // plink2.cc:2998-3001
-          die(7, "Error: --clump requires a sorted .pvar/.bim.  Retry this command after using\n--make-pgen/--make-bed + --sort-vars to sort your data.\n");
-        }
-        die(6, "Error: --r[2]-[un]phased runs require a sorted .pvar/.bim.  Retry this command\nafter using --make-pgen/--make-bed + --sort-vars to sort your data.\n");  // plink2.cc:2944-2947
-      }
-    }
-  }
-
-  // chrX and chrY variants run on engines of their own (different sample sets); MT stays with the autosomes --
-  // except under --indep-pairphase, where the autosomes carry two haplotypes per founder and MT one
-  // (IndepPairphaseUpdateSubcontig, plink2_ld.cc:1491-1511)
-  std::vector<uint32_t>&mk = S.mk, &xk = S.xk, &yk = S.yk, &tk = S.tk;
-  for (uint32_t k = 0; k < variant_ct; ++k) {
-    (vcls[k] == 3 ? xk : (vcls[k] == 4 ? yk : ((vcls[k] == 5 && A.pairphase) ? tk : mk))).push_back(k);
-  }
-  S.m_ct = static_cast<uint32_t>(mk.size());
-  const uint32_t m_ct = S.m_ct;
-  std::vector<uint32_t>&m_chr = S.m_chr, &m_bps = S.m_bps;
-  m_chr.resize(m_ct);
-  m_bps.resize(m_ct);
-  for (uint32_t q = 0; q < m_ct; ++q) {
-    m_chr[q] = chr_idx[mk[q]];
-    m_bps[q] = bps[mk[q]];
-  }
+  // ---- variant table: strip chromosome 0, chromosome order index, sortedness
+  final_variant_list(S, *filter, drop_by_counts);
+  split_into_engines(S);
   g_log_mute = false;
   if (A.het && A.have_r2) {
     // (the r^2 outputs and --clump keep the host's filters: the variant list is final here.  Beside the prune, or alone, run_prune() calls the

@@ -87,11 +87,9 @@ struct ChromNames {
 
 }  // namespace
 
-void reports_list_variants(Session& S, bool chr_filter, const std::unordered_set<std::string>& extract_ids, const std::unordered_set<std::string>& exclude_ids,
-                           std::vector<uint32_t>* listed) {
+void reports_list_variants(Session& S, VariantFilter& filter, std::vector<uint32_t>* listed) {
   const Args& A = S.A;
   const Variants& V = S.V;
-  const uint32_t raw_variant_ct = static_cast<uint32_t>(V.id.size());
   const char* what = A.rep_missing ? "--missing" : (A.rep_freq ? "--freq" : "--geno-counts");
   if (ldp_pgen_has_dosage(S.pg)) {
     // (the reference counts dosages where a record has them -- ALT_FREQS, OBS_CT and the missing-dosage columns' cousins: plink2_data.cc:2421-2443)
@@ -103,40 +101,24 @@ void reports_list_variants(Session& S, bool chr_filter, const std::unordered_set
       die(63, "Error: the sample file carries a phenotype ('%s'), and the phenotype columns of .smiss are not supported by plink2-hip: use --missing variant-only, or plink2.\n", pheno.c_str());
     }
   }
-  std::unordered_map<std::string, uint8_t> chr_state;  // 1 = filtered out by chromosome
   listed->clear();
-  for (uint32_t v = 0; v < raw_variant_ct; ++v) {
-    auto it = chr_state.find(V.chrom[v]);
-    if (it == chr_state.end()) {
-      const std::string& cur = V.chrom[v];
-      const int code = chrom_code(cur);
-      const bool out = chr_filter && (((!A.chr_keep.empty()) && !chrom_listed(A.chr_keep, cur)) || ((!A.chr_drop.empty()) && chrom_listed(A.chr_drop, cur)) ||
-                                       (A.autosome && !((code >= 1) && (code <= 22))));
-      if (!out) {
-        bool zero = false;
-        const int cls = chrom_class(cur, A.allow_extra_chr, &zero);
-        if (cls == 2) {
+  filter.walk(
+      [&](const std::string& cur, const ChromFacts& c) {
+        if ((!c.out) && (c.cls == 2)) {
           die(6, "Error: Invalid chromosome code '%s'. (Use --allow-extra-chr to force it to be accepted.)\n", cur.c_str());
         }
-        if (cls >= 3) {
+        if ((!c.out) && (c.cls >= 3)) {
           // (the haploid genotype columns, the male-only observation counts of chrY and the chrX allele weights are not built)
           die(63, "Error: %s with chrX, chrY or MT variants ('%s') is not supported by plink2-hip: filter them out (--autosome, --chr, --not-chr) or use plink2.\n", what, cur.c_str());
         }
-      }
-      it = chr_state.emplace(cur, static_cast<uint8_t>(out)).first;
-    }
-    if (it->second || ((!A.extract_files.empty()) && !extract_ids.count(V.id[v])) || ((!A.exclude_files.empty()) && exclude_ids.count(V.id[v]))) {
-      continue;
-    }
-    if ((allele_ct_for_filter(V, v) > A.max_alleles) || (A.snps_only && V.not_snp[v])) {
-      continue;
-    }
-    if (A.rep_gcount && (V.alt_ct[v] > 1)) {
-      // (HET_REF_ALT_CTS / TWO_ALT_GENO_CTS list every genotype pair of the alleles: nobody counts those here)
-      die(63, "Error: --geno-counts with a multiallelic variant ('%s') is not supported by plink2-hip: --max-alleles 2 leaves them out.\n", V.id[v].c_str());
-    }
-    listed->push_back(v);
-  }
+      },
+      [&](uint32_t v, const ChromFacts&) {
+        if (A.rep_gcount && (V.alt_ct[v] > 1)) {
+          // (HET_REF_ALT_CTS / TWO_ALT_GENO_CTS list every genotype pair of the alleles: nobody counts those here)
+          die(63, "Error: --geno-counts with a multiallelic variant ('%s') is not supported by plink2-hip: --max-alleles 2 leaves them out.\n", V.id[v].c_str());
+        }
+        listed->push_back(v);
+      });
 }
 
 void reports_count_alleles_host(const Session& S, uint32_t raw_variant, std::vector<uint8_t>* lo, std::vector<uint8_t>* hi, std::vector<uint32_t>* counts) {
